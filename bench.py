@@ -2,7 +2,7 @@
 """Headline benchmark: NlosPose training step (forward + loss + backward + Adam) on
 synthetic 128x128x512 transients, batch 4 per GPU, fp32 (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU; for N > 1 gradients are averaged with bucketed RCCL all-reduce
@@ -12,7 +12,10 @@ in the environment) and --gpus N > 1, this process starts the N ranks itself -- 
 processes under torch.distributed.run, before anything here has touched the GPU -- relays
 their output and exits with their status.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line (with --dump-outputs DIR it first writes what the
+last timed step returned as DIR/<name>.npy).  Everything else -- the per-kernel table and roofline of appended profiled
+steps, the other shapes and precisions under `extra`, the exchange-algorithm A/B and the CPU baseline -- runs only with
+--full.  Extra objects on a --full line:
   roofline     -- the dominant hand-written HIP kernel of the timed region, timed with HIP
                   events on its launch stream inside the library (hp_profile_*); achieved =
                   algorithmic bytes (or flops) per launch / mean launch duration.
@@ -42,6 +45,28 @@ WORKLOADS = {
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense f32-input MFMA peak
 MFMA_BF16_PEAK_TFLOPS = 2516.8  # same guide: dense bf16 MFMA = 16 x the f32-input rate (~2.5 PF)
+DUMP_MAX_ELEMS = 1 << 22    # --dump-outputs: 16 MB of float32 per array at most (a handful of arrays: < 64 MB in all)
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: write each tensor as <path>/<name>.npy in float32.  A tensor of more than DUMP_MAX_ELEMS elements is
+    reduced to a fixed sample of its flattened values (indices drawn from a generator seeded by the tensor's size: the
+    same every run), so that two builds can be compared output for output."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(410 + t.numel())
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+
+def flat_params(params) -> torch.Tensor:
+    """Every tensor of `params` (None skipped) flattened and concatenated in order, float32."""
+    return torch.cat([p.detach().float().reshape(-1) for p in params if p is not None])
 
 
 def posenet_conv_flops(T: int, N: int, B: int) -> dict:
@@ -236,11 +261,13 @@ def bench_sformer(args, emit=True):
     _lib.profile_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        model(video)
+        out = model(video)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     _lib.profile_enable(False)
     prof = _lib.profile_read()
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"joints": out})
     ntok = 24 + 16 * 1024
     attn_flops = 8 * (B * 8 * 16 * 1024 * (24 + 1024) * 32 * 4 + B * 8 * 24 * ntok * 32 * 4)
     ms = prof.get("sformer_attention_patch", (0, 0.0))[1] + prof.get("sformer_attention_joint", (0, 0.0))[1]
@@ -288,14 +315,16 @@ def bench_ingest(args, emit=True):
     torch.cuda.synchronize()
     _lib.profile_reset()
     _lib.profile_enable(True)
-    steps = max(args.steps, 20)
+    steps = args.steps
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     _lib.profile_enable(False)
     prof = _lib.profile_read()
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"meas": out[0], "vol": out[1]})
     px_all, px_kept = 600 * 256 * 256, 512 * 256 * 256
     name = "ingest_rgbe_to_meas"
     alg = 4.0 * px_kept + 4.0 * 128 ** 3  # fused pass: every kept RGBE pixel read once, the volume written once
@@ -313,7 +342,7 @@ def bench_ingest(args, emit=True):
                      "algorithmic_bytes": alg,
                      "note": f"the two global-max passes read 4 B x {px_all} pixels each in addition"},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import numpy as np
 
@@ -369,6 +398,7 @@ def bench_highres(args, emit=True, also_bf16=False):
         f = ops.normalize_feature(fp(fe(meas), [0] * B, [T] * B))
         r = un(f)
         (r.square().mean() + f.mean()).backward()
+        return r, f
 
     for _ in range(args.warmup):
         step()
@@ -377,12 +407,14 @@ def bench_highres(args, emit=True, also_bf16=False):
     _lib.profile_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     _lib.profile_enable(False)
     ops.set_dconv_precision("fp32")
     prof = _lib.profile_read()
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"unet_out": out[0], "feature": out[1], "param_grads": flat_params(p.grad for p in params)})
     V = T * N * N
     lct_ms = sum(v[1] for k, v in prof.items() if k.startswith("lct_"))
     lct_calls = 2 * args.steps  # forward + backward per step
@@ -565,7 +597,15 @@ def main():
                          "(BASELINE configs[2]), fp32 otherwise")
     ap.add_argument("--cpu-baseline-full", action="store_true",
                     help="all legs of BASELINE.md section 3 in cpu_baseline (adds batch 4 at 128^3 and the LCT at 1024x256x256: minutes)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short 128^3 (reference-native shape) run reported under `extra`")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the short runs of other shapes / precisions "
+                                                             "(and the exchange-algorithm A/B) reported under `extra`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: appended profiled steps (per-kernel table, "
+                         "roofline), the other shapes / precisions / workloads under `extra`, the exchange-algorithm A/B and the "
+                         "CPU baseline (a plain run only sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; a fixed "
+                         "sample of any large array; same inputs every run)")
     args = ap.parse_args()
 
     if args.workload == "sformer":
@@ -673,36 +713,42 @@ def main():
     t0 = time.perf_counter()
     losses = []
     for _ in range(args.steps):
-        loss, _, _ = step()
+        loss, jl_last, vl_last = step()
         losses.append(loss)          # device scalars: read back after the timed region
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what a caller of the train step receives: the three losses it returns and the parameters Adam left in the model
+        dump_outputs(args.dump_outputs, {"loss": losses[-1], "joint_loss": jl_last, "voxel_loss": vl_last,
+                                         "params": flat_params(model.parameters())})
     dp_timing = None
     if reducer is not None:
         dp_timing = reducer.read_timing()
         reducer.enable_timing(False)
-    # appended, untimed: `--profile-steps` more steps of the same training run with every kernel family bracketed by HIP
+    # --full: appended, untimed: `--profile-steps` more steps of the same training run with every kernel family bracketed by HIP
     # events on its launch stream and the weight gradients back on the MAIN stream -- one kernel in flight at a time, so the
     # durations measure the kernels themselves.  Also timed as a whole: the un-overlapped step, for the A/B on the line.
-    _ops.set_wgrad_async(False)
-    step()                           # the first step after the switch re-times allocator blocks: not profiled
-    torch.cuda.synchronize()
-    _lib.profile_reset()
-    _lib.profile_enable(1)
-    psteps = max(1, args.profile_steps)
-    tp0 = time.perf_counter()
-    for _ in range(psteps):
-        step()
-    torch.cuda.synchronize()
-    profiled_ms = 1e3 * (time.perf_counter() - tp0) / psteps
-    _lib.profile_enable(False)
-    prof = _lib.profile_read()
-    _ops.set_wgrad_async(wgrad_stream)
+    prof = {}
+    if args.full:
+        _ops.set_wgrad_async(False)
+        step()                           # the first step after the switch re-times allocator blocks: not profiled
+        torch.cuda.synchronize()
+        _lib.profile_reset()
+        _lib.profile_enable(1)
+        psteps = max(1, args.profile_steps)
+        tp0 = time.perf_counter()
+        for _ in range(psteps):
+            step()
+        torch.cuda.synchronize()
+        profiled_ms = 1e3 * (time.perf_counter() - tp0) / psteps
+        _lib.profile_enable(False)
+        prof = _lib.profile_read()
+        _ops.set_wgrad_async(wgrad_stream)
     dp_ab = None
-    if reducer is not None and not args.no_extra:
+    if reducer is not None and args.full and not args.no_extra:
         # the same step with each exchange algorithm, 3 timed steps each (1 warm-up), slowest rank: the first multi-GPU run
         # A/Bs them by itself (the xGMI mesh favours the direct forms, nothing here has measured it)
         dp_ab = {}
@@ -739,7 +785,7 @@ def main():
         ranks_seen = [None] * world
         dist.all_gather_object(ranks_seen, dict(device_identity(local), rank=rank, local_rank=int(os.environ.get("LOCAL_RANK", "0"))))
     dist_extra = None
-    if world > 1 and args.workload == "t512" and not args.no_extra and args.conv_precision == "fp32":
+    if world > 1 and args.full and args.workload == "t512" and not args.no_extra and args.conv_precision == "fp32":
         # BASELINE configs[2]: batch 32 = 8 x 4 in bf16 (matrix cores + activation storage) with fp32 LCT, bf16 on the wire;
         # at other world sizes the same per-GPU share
         if reducer is not None:
@@ -830,12 +876,13 @@ def main():
             cf = posenet_conv_flops(T, N, B)
             line["mfma_tflops_by_kernel"] = {k: round(cf[k] * psteps / (prof[k][1] / 1e3) / 1e12, 1)
                                              for k in sorted(cf) if k in prof and prof[k][1] > 0}
-        line["roofline"] = roof
+        if args.full:
+            line["roofline"] = roof
         if dist_extra is not None:
             line["extra"] = {"configs2_bf16s_dp": dist_extra}
         if dp_ab is not None:
             line.setdefault("extra", {})["dp_algo_ab"] = dp_ab
-        if world == 1 and args.workload == "t512" and not args.no_extra:
+        if world == 1 and args.full and args.workload == "t512" and not args.no_extra:
             # SURVEY 8(d) names two shapes for configs[1]: the BASELINE-worded 128x128x512 cube (the headline above) and
             # the reference's own training shape 128^3 (train.py:77-86); the second is reported here, same step, same batch
             del step
@@ -850,7 +897,7 @@ def main():
                 # BASELINE configs[3] and configs[4] on the same driver line (short runs; their own workloads give the long form)
                 torch.cuda.empty_cache()
                 sub = argparse.Namespace(**vars(args))
-                sub.steps, sub.warmup, sub.batch = 3, 1, 0
+                sub.steps, sub.warmup, sub.batch, sub.dump_outputs = 3, 1, 0, None
                 hr = bench_highres(sub, emit=False, also_bf16=True)
                 line["extra"]["configs3_highres"] = {k: hr[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup",
                                                                         "config", "roofline", "thin_channel_convolutions",
@@ -863,11 +910,11 @@ def main():
                                                                              "dtype", "config", "roofline")}
                 note(f"extra: sformer {sf['ms_per_step']:.1f} ms/step")
                 torch.cuda.empty_cache()
-                sub.no_cpu_baseline = True
+                sub.no_cpu_baseline, sub.steps, sub.dump_outputs = True, 20, None
                 ig = bench_ingest(sub, emit=False)   # one dataset sample -> network inputs on the device
                 line["extra"]["ingest"] = {k: ig[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "config", "roofline")}
                 note(f"extra: ingest {ig['ms_per_step']:.3f} ms/sample")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the box's CPU share for one GPU is 16 cores: more threads than that only oversubscribe
             try:
                 avail = len(os.sched_getaffinity(0))

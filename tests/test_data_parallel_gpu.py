@@ -193,7 +193,7 @@ def _run_bench(extra_args, env_extra, timeout=600, no_extra=True):
         env.pop(k, None)       # the rccl_world1 fixture of this module exports a rendezvous of its own
     env.update(env_extra)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"] + (["--no-extra"] if no_extra else []) + extra_args, env=env, capture_output=True, text=True,
+                        "--no-cpu-baseline"] + (["--no-extra"] if no_extra else ["--full"]) + extra_args, env=env, capture_output=True, text=True,
                        timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -8,11 +8,11 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 R=${1:-round4}
 O=gpurun_out/prof_$R
 rm -rf "$O"; mkdir -p "$O" profiles
-A="--steps 3 --warmup 1 --no-cpu-baseline --no-extra"
+A="--steps 3 --warmup 1 --full --no-cpu-baseline --no-extra"
 rocprofv3 --kernel-trace --stats -d $O/stats -o t512 --output-format csv -- python3 bench.py $A > $O/t512_bench.json 2> $O/t512_bench.err || exit 2
 # (steps executed by the command: 1 warm-up + 2 timed + 1 after the stream switch + 1 profiled = 5: the divisor below)
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/fetch -o f --output-format csv -- python3 bench.py --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --no-extra > /dev/null 2> $O/fetch.err || exit 3
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/write -o w --output-format csv -- python3 bench.py --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --no-extra > /dev/null 2> $O/write.err || exit 4
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/fetch -o f --output-format csv -- python3 bench.py --steps 2 --warmup 1 --full --profile-steps 1 --no-cpu-baseline --no-extra > /dev/null 2> $O/fetch.err || exit 3
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/write -o w --output-format csv -- python3 bench.py --steps 2 --warmup 1 --full --profile-steps 1 --no-cpu-baseline --no-extra > /dev/null 2> $O/write.err || exit 4
 f=$(find $O/stats -name 't512_kernel_stats.csv' | head -1); cp "$f" profiles/${R}_t512_rocprofv3_kernel_stats.csv
 tail -1 $O/t512_bench.json > profiles/${R}_t512_bench_under_rocprof.json
 # round 4: the default command overlaps the weight gradients with the rest of backward (two kernels in flight: contended durations
