@@ -1,10 +1,10 @@
 """NlosPoseSformer: divided space-time transformer head with joint tokens and axial RoPE.
 
-Drop-in (inference) for models/NlosPoseSformer.py `NlosPoseSformer(**kwargs)` (:11-151): same constructor
+Drop-in for models/NlosPoseSformer.py `NlosPoseSformer(**kwargs)` (:11-151): same constructor
 keywords, same state_dict keys (including the time-attention weights that the reference allocates
 but never runs, :66,:133-134), `forward(video (b, f, c, H, W)) -> (b, num_joints, 4, out_dim/4)`.
-All arithmetic runs in libhiddenpose_hip.so (csrc/sformer_kernels.hip + the fp32 MFMA GEMM); the
-reference has no training loop for this orphan head, so only the forward pass is provided.
+All arithmetic runs in libhiddenpose_hip.so (csrc/sformer_kernels.hip, csrc/sformer_backward.hip + the
+fp32 MFMA GEMM and its convolution gradients); autograd trains it through _xformer_autograd.SformerFunction.
 """
 from __future__ import annotations
 
@@ -16,6 +16,7 @@ from torch import nn
 
 from . import _lib
 from . import _xformer as _xf
+from . import _xformer_autograd as _xa
 
 
 class RotaryEmbedding(nn.Module):
@@ -90,6 +91,7 @@ class NlosPoseSformer(nn.Module):
         assert rotary_emb, "only the rotary-embedding variant (config_noise.py:51) is built"
         _lib.lib()
         self.heads, self.dim_head, self.patch_size, self.num_joints = heads, dim_head, patch_size, num_joints
+        self.attn_dropout, self.ff_dropout = attn_dropout, ff_dropout
         patch_dim = channels * patch_size ** 2
         self.to_patch_embedding = nn.Linear(patch_dim, dim)
         self.joints_token = nn.Parameter(torch.zeros(1, num_joints, dim))
@@ -101,11 +103,30 @@ class NlosPoseSformer(nn.Module):
                            _PreNorm(dim, _FeedForward(dim))]) for _ in range(depth)])
         self.to_out = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, out_dim))
 
-    @torch.no_grad()
     def forward(self, video, mask=None):
+        """An autograd graph is built when grad mode is on, the module is in training mode or `video` requires grad, and
+        something (a parameter or `video`) requires grad.  Its forward runs the same kernels in the same order as the
+        no-graph path (the output is bit-identical) and keeps what backward needs; backward needs
+        attention_precision "fp32" and no dropout.  Otherwise (eval mode on a plain input, or no_grad) the no-graph path
+        runs, launch for launch as an inference-only module would."""
         assert mask is None, "frame masks are ignored by the reference's attention (:177-179) and not supported"
         if not video.is_cuda:
             raise _lib.HiddenPoseHipError("NlosPoseSformer.forward needs a tensor on a HIP device; there is no CPU path")
+        params = _xa.trainable_params(self)
+        if (torch.is_grad_enabled() and (self.training or video.requires_grad)
+                and (video.requires_grad or any(p.requires_grad for p in params))):
+            if self.attn_dropout > 0 or self.ff_dropout > 0:
+                raise _lib.HiddenPoseHipError("NlosPoseSformer training: dropout is not built (attn_dropout / ff_dropout must be 0)")
+            aprec = {"fp32": 0, "bf16": 1, "fp16": 4}[self.attention_precision]
+            if aprec and self.dim_head != 32:
+                raise _lib.HiddenPoseHipError("bf16 / fp16 attention is built for dim_head 32 only")
+            with torch.cuda.device(video.device):
+                return _xa.SformerFunction.apply(video.contiguous().float(), self, _LINEAR_PRECISION[self.linear_precision], aprec,
+                                                 *params)
+        with torch.no_grad():
+            return self._forward_nograd(video)
+
+    def _forward_nograd(self, video):
         L = _lib.lib()
         video = video.contiguous().float()
         b, f, c, H, W = video.shape

@@ -129,6 +129,20 @@ SIGNATURES = {
     "hp_box_downsample_round": (_i, [_fp, _fp, _i, _i, _i, C.c_long, C.c_long, C.c_long, _vp]),
     "hp_pair_average_axis0": (_i, [_fp, _fp, _i, _i, _i, C.c_long, C.c_long, C.c_long, _vp]),
     "hp_sformer_attention": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "hp_sformer_attention_lse": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "hp_sformer_attention_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "hp_sformer_attention_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i,
+                                           _vp, _sz, _vp]),
+    "hp_sformer_qkv_prepare_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, C.c_float, _fp, _fp, _i, _vp]),
+    "hp_layernorm_backward_workspace_bytes": (_sz, [C.c_long, _i]),
+    "hp_layernorm_backward": (_i, [_fp, _fp, _fp, _fp, _fp, C.c_long, _i, _fp, C.c_float, _i, C.c_long, _vp, _sz, _vp]),
+    "hp_geglu_backward": (_i, [_fp, _fp, _fp, C.c_long, _i, _vp]),
+    "hp_linear_backward_data_workspace_bytes": (_sz, [_i, _i]),
+    "hp_linear_backward_data": (_i, [_fp, _fp, _fp, _fp, C.c_long, _i, _i, _i, _vp, _sz, _vp]),
+    "hp_linear_backward_weight_workspace_bytes": (_sz, [C.c_long, _i, _i]),
+    "hp_linear_backward_weight": (_i, [_fp, _fp, _fp, _fp, C.c_long, _i, _i, _i, _vp, _sz, _vp]),
+    "hp_sformer_unpatchify": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
+    "hp_sformer_joint_token_backward": (_i, [_fp, _fp, _i, _i, C.c_long, _i, _vp]),
 }
 
 

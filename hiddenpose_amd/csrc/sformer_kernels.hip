@@ -128,11 +128,13 @@ __global__ __launch_bounds__(ST) void k_qkv_prepare(const float* __restrict__ qk
 // mode 0 (patch): grid (ceil(n/128), B*heads*frames); queries = the frame's n patch tokens,
 //                 keys = [nj joint tokens | the frame's n patch tokens].
 // mode 1 (joint): grid (1, B*heads); queries = the nj joint tokens, keys = all Ntok tokens, split over waves.
-template <int DH>
+// LSE: also store lse = m + ln(l) of every patch query (its log-sum-exp over its key set, on the pre-scaled scores; the
+// training path's backward recomputes P from it); the arithmetic of `out` is the same in both instantiations.
+template <int DH, bool LSE = false>
 __global__ __launch_bounds__(ST) void k_attention(const float* __restrict__ Q, const float* __restrict__ K,
                                                   const float* __restrict__ V, float* __restrict__ out, int heads,
                                                   int Ntok, int nj, int n, int frames, int mode,
-                                                  float* __restrict__ part) {
+                                                  float* __restrict__ part, float* __restrict__ lse = nullptr) {
   constexpr int LD = DH + 1;
   __shared__ float Ks[4][32 * LD];
   __shared__ float Vs[4][32 * LD];
@@ -252,6 +254,7 @@ __global__ __launch_bounds__(ST) void k_attention(const float* __restrict__ Q, c
       const int d = (r & 3) + 8 * (r >> 2) + 4 * half;
       if (d < DH) os[col * LD + d] = oacc[r] * inv;
     }
+    if (LSE && qvalid && half == 0) lse[(long)bh * Ntok + qtok] = m + logf(l);
     __syncthreads();
     for (int i = lane; i < 32 * DH; i += 64) {
       const int qr = i / DH, d = i - qr * DH;
@@ -437,8 +440,9 @@ __global__ __launch_bounds__(ST) void k_attention_patch_h16(const float* __restr
 }
 
 // merge the key splits of the joint-token attention: one thread per (bh, query, d)
+// (lse != nullptr: also store the joint queries' log-sum-exp over all Ntok keys, M + ln(L))
 __global__ void k_attention_joint_merge(const float* __restrict__ part, float* __restrict__ out, int BH, int heads, int dh,
-                                        int Ntok, int nq, int nsplit) {
+                                        int Ntok, int nq, int nsplit, float* __restrict__ lse = nullptr) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= BH * nq * dh) return;
   const int d = i % dh, qr = (i / dh) % nq, bh = i / (dh * nq);
@@ -454,6 +458,7 @@ __global__ void k_attention_joint_merge(const float* __restrict__ part, float* _
     o += rec[d] * sc;
   }
   out[((long)b * Ntok + qr) * heads * dh + head * dh + d] = o / L;
+  if (lse && d == 0) lse[(long)bh * Ntok + qr] = M + logf(L);
 }
 
 static unsigned sgrid(long n) { return (unsigned)std::max<long>(1, std::min<long>((n + ST - 1) / ST, 256 * 8)); }
@@ -559,6 +564,41 @@ extern "C" int hp_sformer_attention(const float* Q, const float* K, const float*
     const int total = B * heads * num_joints * dh;
     hipLaunchKernelGGL(k_attention_joint_merge, dim3((total + 255) / 256), dim3(256), 0, st, part, out, B * heads, heads, dh, Ntok,
                        num_joints, nsplit);
+  }
+  HP_CHECK_HIP(hipGetLastError());
+  return HP_OK;
+}
+
+// hp_sformer_attention in fp32 with the log-sum-exp of every query (the training path's forward): the same launches, the
+// patch kernel's LSE instantiation and the merge's lse store; `out` is bit-identical to hp_sformer_attention's.
+extern "C" int hp_sformer_attention_lse(const float* Q, const float* K, const float* K0, const float* V, float* out, float* lse, int B,
+                                        int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames, void* workspace,
+                                        void* stream) {
+  HP_REQUIRE(Q && K && K0 && V && out && lse && workspace, "hp_sformer_attention_lse: null argument");
+  HP_REQUIRE(num_joints <= 32 && Ntok == num_joints + frames * patches_per_frame, "hp_sformer_attention_lse: bad token layout");
+  if (dh != 16 && dh != 24 && dh != 32) {
+    set_error("hp_sformer_attention_lse: dim_head %d not built (16, 24, 32)", dh);
+    return HP_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int ntiles = (Ntok + 31) / 32;
+  const int nsplit = std::max(1, std::min(JOINT_SPLITS, ntiles / 4));
+  float* part = (float*)workspace;
+  const dim3 gp((patches_per_frame + 127) / 128, B * heads * frames), gj(nsplit, B * heads);
+  {
+    HP_PROF("sformer_attention_patch", st);
+    if (dh == 32) hipLaunchKernelGGL((k_attention<32, true>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 0, part, lse);
+    else if (dh == 24) hipLaunchKernelGGL((k_attention<24, true>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 0, part, lse);
+    else hipLaunchKernelGGL((k_attention<16, true>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 0, part, lse);
+  }
+  if (num_joints > 0) {
+    HP_PROF("sformer_attention_joint", st);
+    if (dh == 32) hipLaunchKernelGGL((k_attention<32>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
+    else if (dh == 24) hipLaunchKernelGGL((k_attention<24>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
+    else hipLaunchKernelGGL((k_attention<16>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
+    const int total = B * heads * num_joints * dh;
+    hipLaunchKernelGGL(k_attention_joint_merge, dim3((total + 255) / 256), dim3(256), 0, st, part, out, B * heads, heads, dh, Ntok,
+                       num_joints, nsplit, lse);
   }
   HP_CHECK_HIP(hipGetLastError());
   return HP_OK;

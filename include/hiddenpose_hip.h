@@ -466,6 +466,56 @@ int hp_sformer_attention(const float* Q, const float* K, const float* K0, const 
                          void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------
+ * NlosPoseSformer backward (training path of NlosPoseSformer.forward).  Every reduction runs in a fixed order: two calls
+ * on the same inputs give identical outputs, except the Linear weight gradient (the convolution weight gradient's split
+ * reduction meets in fp32 atomics).
+ * ---------------------------------------------------------------------- */
+/* hp_sformer_attention in fp32 (same workspace) that also writes lse (B, heads, Ntok): the natural-log sum of exp of every
+ * query's scores over its own key set (patch queries: [joint tokens | their frame]; joint queries: all tokens), on the
+ * pre-scaled scores.  `out` is bit-identical to hp_sformer_attention(..., HP_PRECISION_FP32, ...). */
+int hp_sformer_attention_lse(const float* Q, const float* K, const float* K0, const float* V, float* out, float* lse, int B,
+                             int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames, void* workspace,
+                             void* stream);
+/* Gradients dQ, dK, dK0, dV (B, heads, Ntok, dh) of the fp32 attention from Q, K, K0, V, its output `out` and lse and the
+ * incoming gradient dout (both in the merged (B, Ntok, heads * dh) layout).  dK0 is the gradient through the joint
+ * queries' keys (K0); dK the one through the patch queries' keys (RoPE on patch rows).  Exact fp32, dh 16 / 24 / 32,
+ * 0 <= num_joints <= 32. */
+size_t hp_sformer_attention_backward_workspace_bytes(int B, int heads, int dh, int Ntok, int num_joints, int frames);
+int hp_sformer_attention_backward(const float* Q, const float* K, const float* K0, const float* V, const float* out,
+                                  const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B,
+                                  int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+/* Transpose of hp_sformer_qkv_prepare: dqkv (B, Ntok, 3 * heads * dh) = [scale R^T(dQ) | R^T(dK) + dK0 | dV], R^T the
+ * inverse rotation on the patch tokens' first rot_dim dims (identity on the joint tokens). */
+int hp_sformer_qkv_prepare_backward(const float* dQ, const float* dK, const float* dK0, const float* dV, float* dqkv, int B,
+                                    int Ntok, int heads, int dh, int num_joints, int patches_per_frame, float scale,
+                                    const float* sin_t, const float* cos_t, int rot_dim, void* stream);
+/* LayerNorm backward with the forward's row addressing (rows_per_batch / batch_stride_rows select rows of x and dx; dy is
+ * (rows, dim)).  ADDS LN^T(dy) into dx (the residual stream's gradient) and WRITES dgamma, dbeta.  mean and rstd are
+ * recomputed from x as hp_layernorm_forward computes them.  dim <= 1024. */
+size_t hp_layernorm_backward_workspace_bytes(long rows, int dim);
+int hp_layernorm_backward(const float* x, const float* dy, float* dx, float* dgamma, float* dbeta, long rows, int dim,
+                          const float* gamma, float eps, int rows_per_batch, long batch_stride_rows, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* GEGLU backward: du (rows, 2 hidden) from the GEMM output u (rows, 2 hidden) and dg (rows, hidden), exact erf GELU. */
+int hp_geglu_backward(const float* u, const float* dg, float* du, long rows, int hidden, void* stream);
+/* nn.Linear data gradient dx (M, K) = dy (M, N) @ w (N, K) [+ addend] (addend may be NULL, must not be dx): the 1x1x1
+ * convolution data gradient with its packed weight image built into the workspace.  precision as the forward's. */
+size_t hp_linear_backward_data_workspace_bytes(int K, int N);
+int hp_linear_backward_data(const float* dy, const float* w, const float* addend, float* dx, long M, int K, int N,
+                            int precision, void* workspace, size_t workspace_bytes, void* stream);
+/* nn.Linear weight gradient dw (N, K) = dy^T x in torch layout (the 1x1x1 convolution weight gradient), and db (N) = the
+ * column sums of dy (may be NULL) in a fixed order. */
+size_t hp_linear_backward_weight_workspace_bytes(long M, int K, int N);
+int hp_linear_backward_weight(const float* x, const float* dy, float* dw, float* db, long M, int K, int N, int precision,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* gradient of hp_sformer_patchify: tokens ((b f h w), (p1 p2 c)) -> video (b, f, c, H, W) */
+int hp_sformer_unpatchify(const float* tokens, float* video, int B, int frames, int C, int H, int W, int patch,
+                          void* stream);
+/* joints_token gradient: djt (num_joints, dim) = sum over the batch of dx[b, :num_joints] (dx (B, Ntok, dim)) */
+int hp_sformer_joint_token_backward(const float* dx, float* djt, int B, int num_joints, long Ntok, int dim, void* stream);
+
+/* ------------------------------------------------------------------------
  * Measurement ingest (utils/nlos_pose_dataloader.py:71-144, utils/loadrealdata.py:6-15): the per-sample
  * CPU work of the reference's Dataset.__getitem__, moved to the device.
  * ---------------------------------------------------------------------- */

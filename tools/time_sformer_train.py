@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""NlosPoseSformer training-step timing at the BASELINE config-5 geometry (dim 256, depth 8, 8 x 32 heads, patch 4, 16 frames
+of 128^2, fp32, seeded input): no-graph forward, graph-mode forward, backward, the library's per-kernel profile of one
+step, the attention backward's rate on the five-product count and the peak device memory.  One JSON line.
+
+    python tools/time_sformer_train.py [--batch 8] [--steps 5] [--warmup 2]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from hiddenpose_amd import _lib  # noqa: E402
+from hiddenpose_amd import testing as hpt  # noqa: E402
+from hiddenpose_amd.NlosPoseSformer import NlosPoseSformer  # noqa: E402
+
+FP32_MFMA_PEAK = 157.3e12
+
+
+def timed(fn, steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+    kw = dict(dim=256, num_frames=16, num_joints=24, image_size=128, patch_size=4, channels=1, depth=8, heads=8, dim_head=32,
+              out_dim=512)
+    m = NlosPoseSformer(**kw)
+    hpt.fill_module(m, "sformer.")
+    m = m.cuda()
+    B = a.batch
+    video = torch.rand(B, 16, 1, 128, 128, generator=torch.Generator().manual_seed(5)).cuda()
+    R = torch.randn(B, 24, 4, 128, generator=torch.Generator().manual_seed(6)).cuda()
+
+    def fwd_nograd():
+        with torch.no_grad():
+            m.eval()(video)
+
+    state = {}
+
+    def fwd_graph():
+        state["y"] = m.train()(video)
+
+    def step():
+        y = m.train()(video)
+        m.zero_grad(set_to_none=True)
+        (y * R).sum().backward()
+
+    for _ in range(a.warmup):
+        fwd_nograd()
+        step()
+    t_nograd = timed(fwd_nograd, a.steps)
+    t_graph = timed(fwd_graph, a.steps)
+    state.clear()
+    t_step = timed(step, a.steps)
+    torch.cuda.reset_peak_memory_stats()
+    step()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated()
+    # per-kernel times of one step, in a run of its own (HIP events around every launch)
+    _lib.profile_enable(True)
+    _lib.profile_reset()
+    step()
+    torch.cuda.synchronize()
+    prof = _lib.profile_read()
+    _lib.profile_enable(False)
+    f, n, nj, heads, dh, depth = 16, 32 * 32, 24, 8, 32, 8
+    ntok = nj + f * n
+    flops = depth * (5 * 2 * B * heads * f * n * (nj + n) * dh + 5 * 2 * B * heads * nj * ntok * dh)
+    attn_ms = sum(ms for k, (_, ms) in prof.items() if k.startswith("sformer_attn_bwd"))
+    rate = flops / (attn_ms * 1e-3) if attn_ms else 0.0
+    print(json.dumps({
+        "config": "config5", "batch": B, "precision": "fp32",
+        "forward_nograd_ms": round(t_nograd, 2), "forward_graph_ms": round(t_graph, 2),
+        "backward_ms": round(t_step - t_graph, 2), "step_ms": round(t_step, 2), "step_over_nograd_forward": round(t_step / t_nograd, 2),
+        "attention_backward_ms": round(attn_ms, 2), "attention_backward_tflops": round(rate / 1e12, 1),
+        "attention_backward_fraction_of_fp32_mfma_peak": round(rate / FP32_MFMA_PEAK, 3),
+        "peak_memory_gb": round(peak / 1e9, 2),
+        "kernels_ms": {k: [cnt, round(ms, 3)] for k, (cnt, ms) in sorted(prof.items(), key=lambda kv: -kv[1][1])},
+    }))
+
+
+if __name__ == "__main__":
+    main()
