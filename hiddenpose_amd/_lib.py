@@ -137,6 +137,10 @@ SIGNATURES = {
     "hp_layernorm_backward_workspace_bytes": (_sz, [C.c_long, _i]),
     "hp_layernorm_backward": (_i, [_fp, _fp, _fp, _fp, _fp, C.c_long, _i, _fp, C.c_float, _i, C.c_long, _vp, _sz, _vp]),
     "hp_geglu_backward": (_i, [_fp, _fp, _fp, C.c_long, _i, _vp]),
+    "hp_gelu_backward": (_i, [_fp, _fp, _fp, C.c_long, _vp]),
+    "hp_sformer_attention_backward_grouped_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "hp_sformer_attention_backward_grouped": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i,
+                                                   _i, _vp, _sz, _vp]),
     "hp_linear_backward_data_workspace_bytes": (_sz, [_i, _i]),
     "hp_linear_backward_data": (_i, [_fp, _fp, _fp, _fp, C.c_long, _i, _i, _i, _vp, _sz, _vp]),
     "hp_linear_backward_weight_workspace_bytes": (_sz, [C.c_long, _i, _i]),

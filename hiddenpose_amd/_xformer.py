@@ -1,7 +1,7 @@
 """Building blocks shared by the transformer heads (transformer.TimeSformer, tokenpose.TokenPose_L_base): every
 arithmetic step is a kernel of libhiddenpose_hip.so (Linear = the MFMA GEMM, LayerNorm, qkv split + rotary,
-flash-style attention, GEGLU / GELU); PyTorch only owns the buffers.  Inference (no autograd): the reference has no
-training loop for these orphan heads."""
+flash-style attention, GEGLU / GELU); PyTorch only owns the buffers.  These are the no-graph (inference) forms; the
+training paths of the heads are in _xformer_autograd.py."""
 from __future__ import annotations
 
 import torch

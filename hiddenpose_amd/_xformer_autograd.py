@@ -1,9 +1,10 @@
-"""Training path of NlosPoseSformer: one torch.autograd.Function whose forward runs the no-graph forward's kernels in the
-same order (so its output is bit-identical) while keeping what the backward needs, and whose backward is a chain of HIP
-kernels (include/hiddenpose_hip.h, "NlosPoseSformer backward").  PyTorch only allocates, zero-fills and copies.
+"""Training paths of the transformer heads (NlosPoseSformer, TimeSformer, TokenPose-L): one torch.autograd.Function per
+head whose forward runs the no-graph forward's kernels in the same order (so its output is bit-identical) while keeping
+what the backward needs, and whose backward is a chain of HIP kernels (include/hiddenpose_hip.h, "NlosPoseSformer
+backward").  PyTorch only allocates, zero-fills and copies.
 
-The op-level helpers (layernorm_backward, linear_backward, geglu_backward) are written for any row-major token matrix, so
-the other transformer heads can reuse them."""
+The op-level helpers (layernorm_backward, linear_backward, geglu_backward, gelu_backward) are written for any row-major
+token matrix; the sublayer helpers (pre-norm attention, GEGLU / GELU feed-forward) serve TimeSformer and TokenPose-L."""
 from __future__ import annotations
 
 import torch
@@ -237,3 +238,435 @@ class SformerFunction(torch.autograd.Function):
             dvideo = torch.empty(b, f, c, H, W, dtype=torch.float32, device=dev)
             _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dvideo.data_ptr(), b, f, c, H, W, ps, st), "hp_sformer_unpatchify")
         return (dvideo, None, None, None, *grads)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# TimeSformer and TokenPose-L training paths.  The sublayer helpers below take the layer input x (b, ntok, dim) and return a
+# fresh x + sublayer(x) together with what their backward needs; their backward ADDS the sublayer's input gradient into dx
+# (the residual stream's gradient, which already holds d(x + sublayer(x))) and returns the parameter gradients.
+
+def gelu_backward(u, dy):
+    """du = dy * gelu'(u) (hp_gelu_backward, written over dy)."""
+    _lib.check(_lib.lib().hp_gelu_backward(u.data_ptr(), dy.data_ptr(), dy.data_ptr(), u.numel(), _st(u)), "hp_gelu_backward")
+    return dy
+
+
+def attention_backward_grouped(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, groups):
+    """attention_backward for short groups (hp_sformer_attention_backward_grouped): n <= 64 tokens per group."""
+    L = _lib.lib()
+    dq, dk, dk0, dv = (torch.empty_like(q) for _ in range(4))
+    nb = L.hp_sformer_attention_backward_grouped_workspace_bytes(b, heads, dh, ntok, nj, groups)
+    ws = _ws(nb, q.device)
+    _lib.check(L.hp_sformer_attention_backward_grouped(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(),
+                                                       dout.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(),
+                                                       dv.data_ptr(), b, heads, dh, ntok, nj, n, groups, ws.data_ptr(), nb, _st(q)),
+               "hp_sformer_attention_backward_grouped")
+    return dq, dk, dk0, dv
+
+
+# time attention's backward: "grouped" (hp_sformer_attention_backward_grouped) or "generic" (hp_sformer_attention_backward);
+# DESIGN 4.4.2 records the A/B that chose it
+TIME_ATTENTION_BACKWARD = "grouped"
+
+
+def time_perm(t, f, n):
+    """[cls | (f, n) frame-major rows] -> [cls | (n, f)]: the time attention's groups become contiguous (a copy)."""
+    b, ntok, d = t.shape
+    o = torch.empty_like(t)
+    o[:, :1] = t[:, :1]
+    o[:, 1:] = t[:, 1:].view(b, f, n, d).transpose(1, 2).reshape(b, n * f, d)
+    return o
+
+
+def time_unperm(t, f, n):
+    """Inverse (and adjoint) of time_perm."""
+    b, ntok, d = t.shape
+    o = torch.empty_like(t)
+    o[:, :1] = t[:, :1]
+    o[:, 1:] = t[:, 1:].view(b, n, f, d).transpose(1, 2).reshape(b, f * n, d)
+    return o
+
+
+def token_shift_adjoint(g, frames, nj=1):
+    """Adjoint of transformer._token_shift: the shifted thirds of the patch rows move back the opposite way (zeros at the
+    clip ends); the other channels and the class rows pass through.  Plain slice copies."""
+    b, ntok, d = g.shape
+    n = (ntok - nj) // frames
+    p = g[:, nj:].view(b, frames, n, d)
+    out = g.clone()
+    o = out[:, nj:].view(b, frames, n, d)
+    c = d // 3
+    o[:, :, :, :c] = 0
+    o[:, 1:, :, :c] = p[:, :-1, :, :c]                      # forward: frame j took frame j + 1
+    o[:, :, :, 2 * c:3 * c] = 0
+    o[:, :-1, :, 2 * c:3 * c] = p[:, 1:, :, 2 * c:3 * c]    # forward: frame j took frame j - 1
+    return out
+
+
+def layernorm(x, w, b, eps, rows, dim, rows_per_batch=0, batch_stride_rows=0):
+    y = torch.empty(rows, dim, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().hp_layernorm_forward(x.data_ptr(), y.data_ptr(), rows, dim, w.data_ptr(), b.data_ptr(), eps, rows_per_batch,
+                                               batch_stride_rows, _st(x)), "hp_layernorm_forward")
+    return y
+
+
+def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t, cos_t, prec, pre=None, perm=None, unperm=None):
+    """x + Wo unperm(Attn(perm(pre(LN(x))))) + bo for the token layout [nj | groups x n] of the permuted rows, as
+    _xformer.attention runs it (fp32 attention, with lse).  p = (ln_w, ln_b, wqkv, wo, bo).  -> (x1, saved)."""
+    L = _lib.lib()
+    ln_w, ln_b, wqkv, wo, bo = p
+    b, ntok, dim = x.shape
+    rows, inner = b * ntok, heads * dh
+    dev = x.device
+    st = _st(x)
+    h = layernorm(x, ln_w, ln_b, eps, rows, dim).view(b, ntok, dim)
+    if pre is not None:
+        h = pre(h)
+    if perm is not None:
+        h = perm(h)
+    qkv = linear(h.view(rows, dim), wqkv, None, prec)
+    q = torch.empty(b, heads, ntok, dh, dtype=torch.float32, device=dev)
+    k, k0, v = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+    rot_dim = 0 if sin_t is None else sin_t.shape[-1]
+    _lib.check(L.hp_sformer_qkv_prepare(qkv.data_ptr(), q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), b, ntok, heads, dh, nj, n,
+                                        scale, _lib.ptr(sin_t), _lib.ptr(cos_t), rot_dim, st), "hp_sformer_qkv_prepare")
+    del qkv
+    att = torch.empty(b, ntok, inner, dtype=torch.float32, device=dev)
+    lse = torch.empty(b, heads, ntok, dtype=torch.float32, device=dev)
+    aws = _ws(L.hp_sformer_attention_workspace_bytes(b, heads, dh), dev)
+    _lib.check(L.hp_sformer_attention_lse(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(), b, heads,
+                                          dh, ntok, nj, n, groups, aws.data_ptr(), st), "hp_sformer_attention_lse")
+    ab = unperm(att) if unperm is not None else att
+    x1 = linear(ab.view(rows, inner), wo, bo, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
+    return x1, (x, h, q, k, k0, v, att, lse, ab)
+
+
+def prenorm_attention_backward(dx, saved, p, eps, scale, heads, dh, nj, n, groups, sin_t, cos_t, prec, pre_adjoint=None, perm=None,
+                               unperm=None, grouped=False):
+    """dx += d(sublayer input); returns [d ln_w, d ln_b, d wqkv, d wo, d bo]."""
+    L = _lib.lib()
+    ln_w, _ln_b, wqkv, wo, _bo = p
+    x, h, q, k, k0, v, att, lse, ab = saved
+    b, ntok, dim = x.shape
+    rows, inner = b * ntok, heads * dh
+    dab, dwo, dbo = linear_backward(ab.view(rows, inner), dx.view(rows, dim), wo, prec)
+    datt = perm(dab.view(b, ntok, inner)) if perm is not None else dab     # the adjoint of unperm is perm
+    del dab
+    bwd = attention_backward_grouped if grouped else attention_backward
+    dq, dk, dk0, dv = bwd(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups)
+    del datt
+    dqkv = torch.empty(rows, 3 * inner, dtype=torch.float32, device=x.device)
+    rot_dim = 0 if sin_t is None else sin_t.shape[-1]
+    _lib.check(L.hp_sformer_qkv_prepare_backward(dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), dqkv.data_ptr(), b, ntok,
+                                                 heads, dh, nj, n, scale, _lib.ptr(sin_t), _lib.ptr(cos_t), rot_dim, _st(dx)),
+               "hp_sformer_qkv_prepare_backward")
+    del dq, dk, dk0, dv
+    dh_, dwqkv, _ = linear_backward(h.view(rows, dim), dqkv, wqkv, prec, with_bias=False)
+    del dqkv
+    dh_ = dh_.view(b, ntok, dim)
+    if unperm is not None:
+        dh_ = unperm(dh_)
+    if pre_adjoint is not None:
+        dh_ = pre_adjoint(dh_)
+    dg, db = layernorm_backward(x, dh_, dx, ln_w, eps, rows, dim)
+    return [dg, db, dwqkv, dwo, dbo]
+
+
+def geglu_ff_forward(x, p, eps, prec, pre=None):
+    """x + W2 GEGLU(W1 pre(LN(x)) + b1) + b2 as _xformer.geglu_ff runs it.  p = (ln_w, ln_b, w1, b1, w2, b2)."""
+    L = _lib.lib()
+    ln_w, ln_b, w1, b1, w2, b2 = p
+    b, ntok, dim = x.shape
+    rows = b * ntok
+    st = _st(x)
+    h = layernorm(x, ln_w, ln_b, eps, rows, dim).view(b, ntok, dim)
+    if pre is not None:
+        h = pre(h)
+    hid = w2.shape[1]
+    g = torch.empty(rows, hid, dtype=torch.float32, device=x.device)
+    if hid % 64 == 0 and w1.shape[0] == 2 * hid:
+        _lib.check(L.hp_linear_geglu_forward(h.data_ptr(), w1.data_ptr(), _lib.ptr(b1), g.data_ptr(), rows, dim, 2 * hid, prec, st),
+                   "hp_linear_geglu_forward")
+    else:
+        u = linear(h.view(rows, dim), w1, b1, prec)
+        _lib.check(L.hp_geglu_forward(u.data_ptr(), g.data_ptr(), rows, hid, st), "hp_geglu_forward")
+        del u
+    x1 = linear(g, w2, b2, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
+    return x1, (x, h, g)
+
+
+def geglu_ff_backward(dx, saved, p, eps, prec, pre_adjoint=None):
+    """dx += d(sublayer input); returns [d ln_w, d ln_b, d w1, d b1, d w2, d b2].  u is recomputed from the saved input."""
+    ln_w, _ln_b, w1, b1, w2, _b2 = p
+    x, h, g = saved
+    b, ntok, dim = x.shape
+    rows = b * ntok
+    dg, dw2, db2 = linear_backward(g, dx.view(rows, dim), w2, prec)
+    u = linear(h.view(rows, dim), w1, b1, prec)
+    du = geglu_backward(u, dg)
+    del u, dg
+    dh_, dw1, db1 = linear_backward(h.view(rows, dim), du, w1, prec)
+    del du
+    dh_ = dh_.view(b, ntok, dim)
+    if pre_adjoint is not None:
+        dh_ = pre_adjoint(dh_)
+    dg_, db_ = layernorm_backward(x, dh_, dx, ln_w, eps, rows, dim)
+    return [dg_, db_, dw1, db1, dw2, db2]
+
+
+def gelu_ff_forward(x, p, eps, prec):
+    """x + W2 gelu(W1 LN(x) + b1) + b2 as _xformer.gelu_ff runs it, with the GELU out of place (u is kept)."""
+    ln_w, ln_b, w1, b1, w2, b2 = p
+    b, ntok, dim = x.shape
+    rows = b * ntok
+    h = layernorm(x, ln_w, ln_b, eps, rows, dim)
+    u = linear(h, w1, b1, prec)
+    a = torch.empty_like(u)
+    _lib.check(_lib.lib().hp_gelu_forward(u.data_ptr(), a.data_ptr(), u.numel(), _st(x)), "hp_gelu_forward")
+    x1 = linear(a, w2, b2, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
+    return x1, (x, h, u, a)
+
+
+def gelu_ff_backward(dx, saved, p, eps, prec):
+    ln_w, _ln_b, w1, _b1, w2, _b2 = p
+    x, h, u, a = saved
+    b, ntok, dim = x.shape
+    rows = b * ntok
+    da, dw2, db2 = linear_backward(a, dx.view(rows, dim), w2, prec)
+    du = gelu_backward(u, da)
+    dh_, dw1, db1 = linear_backward(h, du, w1, prec)
+    del du
+    dg_, db_ = layernorm_backward(x, dh_, dx, ln_w, eps, rows, dim)
+    return [dg_, db_, dw1, db1, dw2, db2]
+
+
+def _joint_sum(dx, rows):
+    """sum over the batch of dx[:, :rows] (hp_sformer_joint_token_backward) -> (1, rows, dim)."""
+    b, ntok, dim = dx.shape
+    out = torch.empty(1, rows, dim, dtype=torch.float32, device=dx.device)
+    _lib.check(_lib.lib().hp_sformer_joint_token_backward(dx.data_ptr(), out.data_ptr(), b, rows, ntok, dim, _st(dx)),
+               "hp_sformer_joint_token_backward")
+    return out
+
+
+def _unwrap(m, shift):
+    return m.fn if shift else m
+
+
+TS_PER_LAYER = 16
+
+
+def timesformer_params(m):
+    """The parameters TimeSformerFunction takes, in its order (every parameter of the module)."""
+    ps = [m.to_patch_embedding.weight, m.to_patch_embedding.bias, m.cls_token]
+    for time_attn, spatial, ff in m.layers:
+        for sub in (time_attn, spatial):
+            a = _unwrap(sub.fn, m.shift_tokens)
+            ps += [sub.norm.weight, sub.norm.bias, a.to_qkv.weight, a.to_out[0].weight, a.to_out[0].bias]
+        f = _unwrap(ff.fn, m.shift_tokens)
+        ps += [ff.norm.weight, ff.norm.bias, f.net[0].weight, f.net[0].bias, f.net[3].weight, f.net[3].bias]
+    return ps + [m.to_out[0].weight, m.to_out[0].bias, m.to_out[1].weight, m.to_out[1].bias]
+
+
+class TimeSformerFunction(torch.autograd.Function):
+    """video (b, f, c, H, W), *timesformer_params(m) -> (b, 72).  Per layer: time attention (the rotary frame tables, on
+    the transposed token grid: groups = hp*wp patch positions of f tokens), space attention (the axial tables, groups = f
+    frames of hp*wp patches), GEGLU feed-forward; token shift before each when m.shift_tokens."""
+
+    @staticmethod
+    def forward(ctx, video, m, prec, *params):
+        from .transformer import _token_shift
+
+        L = _lib.lib()
+        b, f, c, H, W = video.shape
+        ps, heads, dh = m.patch_size, m.heads, m.dim_head
+        hp, wp = H // ps, W // ps
+        n = hp * wp
+        ntok = 1 + f * n
+        dim = m.cls_token.shape[-1]
+        dev = video.device
+        tokens = torch.empty(b * f * n, ps * ps * c, dtype=torch.float32, device=dev)
+        _lib.check(L.hp_sformer_patchify(video.data_ptr(), tokens.data_ptr(), b, f, c, H, W, ps, _st(video)), "hp_sformer_patchify")
+        emb = linear(tokens, params[0], params[1])
+        x = torch.empty(b, ntok, dim, dtype=torch.float32, device=dev)
+        x[:, :1] = params[2]
+        x[:, 1:] = emb.view(b, f * n, dim)
+        del emb
+        sin_s, cos_s = m.image_rot_emb.tables(hp, wp, dev)
+        sin_t, cos_t = m._frame_tables(f, dev)
+        pre = (lambda t: _token_shift(t, f)) if m.shift_tokens else None
+        perm, unperm = (lambda t: time_perm(t, f, n)), (lambda t: time_unperm(t, f, n))
+        saved, consts = [], []
+        for i, (time_attn, spatial, ff) in enumerate(m.layers):
+            lp = params[3 + TS_PER_LAYER * i: 3 + TS_PER_LAYER * (i + 1)]
+            sc_t, sc_s = _unwrap(time_attn.fn, m.shift_tokens).scale, _unwrap(spatial.fn, m.shift_tokens).scale
+            eps = (time_attn.norm.eps, spatial.norm.eps, ff.norm.eps)
+            x, s_t = prenorm_attention_forward(x, lp[0:5], eps[0], sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec, pre, perm, unperm)
+            x, s_s = prenorm_attention_forward(x, lp[5:10], eps[1], sc_s, heads, dh, 1, n, f, sin_s, cos_s, prec, pre)
+            x, s_f = geglu_ff_forward(x, lp[10:16], eps[2], prec, pre)
+            saved += [*s_t, *s_s, *s_f]
+            consts.append((sc_t, sc_s) + eps)
+        cls = layernorm(x, params[-4], params[-3], m.to_out[0].eps, b, dim, 1, ntok)
+        out = linear(cls, params[-2], params[-1])
+        ctx.geom = (b, f, c, H, W, ps, heads, dh, n, ntok, dim, prec, m.shift_tokens, m.to_out[0].eps)
+        ctx.consts = consts
+        ctx.nsaved = len(saved)
+        ctx.save_for_backward(*saved, tokens, x, cls, sin_s, cos_s, sin_t, cos_t, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        b, f, c, H, W, ps, heads, dh, n, ntok, dim, prec, shift, eps_out = ctx.geom
+        L = _lib.lib()
+        allt = ctx.saved_tensors
+        saved = allt[:ctx.nsaved]
+        tokens, xl, cls, sin_s, cos_s, sin_t, cos_t = allt[ctx.nsaved:ctx.nsaved + 7]
+        params = allt[ctx.nsaved + 7:]
+        dev = dout.device
+        grads = [None] * len(params)
+        dout = dout.contiguous()
+        dcls, grads[-2], grads[-1] = linear_backward(cls, dout, params[-2])
+        dx = torch.zeros(b, ntok, dim, dtype=torch.float32, device=dev)
+        grads[-4], grads[-3] = layernorm_backward(xl, dcls, dx, params[-4], eps_out, b, dim, 1, ntok)
+        del dcls
+        pre_adj = (lambda t: token_shift_adjoint(t, f)) if shift else None
+        perm, unperm = (lambda t: time_perm(t, f, n)), (lambda t: time_unperm(t, f, n))
+        grouped = TIME_ATTENTION_BACKWARD == "grouped"
+        per = 9 + 9 + 3
+        for i in reversed(range(len(ctx.consts))):
+            sv = saved[per * i: per * (i + 1)]
+            base = 3 + TS_PER_LAYER * i
+            lp = params[base: base + TS_PER_LAYER]
+            sc_t, sc_s, e_t, e_s, e_f = ctx.consts[i]
+            grads[base + 10: base + 16] = geglu_ff_backward(dx, sv[18:21], lp[10:16], e_f, prec, pre_adj)
+            grads[base + 5: base + 10] = prenorm_attention_backward(dx, sv[9:18], lp[5:10], e_s, sc_s, heads, dh, 1, n, f, sin_s, cos_s,
+                                                                    prec, pre_adj)
+            grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_t, sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec,
+                                                               pre_adj, perm, unperm, grouped=grouped)
+        grads[2] = _joint_sum(dx, 1).view(1, dim)      # cls_token (1, dim), shared by the batch
+        demb = dx[:, 1:].contiguous().view(b * f * n, dim)
+        need_video = ctx.needs_input_grad[0]
+        dtok, grads[0], grads[1] = linear_backward(tokens, demb, params[0], need_dx=need_video)
+        dvideo = None
+        if need_video:
+            dvideo = torch.empty(b, f, c, H, W, dtype=torch.float32, device=dev)
+            _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dvideo.data_ptr(), b, f, c, H, W, ps, _st(dout)), "hp_sformer_unpatchify")
+        return (dvideo, None, None, *grads)
+
+
+TP_PER_LAYER = 11
+
+
+def tokenpose_params(m):
+    """The tensors TokenPoseFunction takes, in its order: patch embedding, keypoint_token, pos_embedding (frozen in the
+    sine modes: requires_grad False, so it gets no gradient), the three stages' layers, the heat-map head."""
+    ps = [m.patch_to_embedding.weight, m.patch_to_embedding.bias, m.keypoint_token, m.pos_embedding]
+    for t in (m.transformer1, m.transformer2, m.transformer3):
+        for attn, ff in t.layers:
+            a, fw = attn.fn.fn, ff.fn.fn
+            ps += [attn.fn.norm.weight, attn.fn.norm.bias, a.to_qkv.weight, a.to_out[0].weight, a.to_out[0].bias, ff.fn.norm.weight,
+                   ff.fn.norm.bias, fw.net[0].weight, fw.net[0].bias, fw.net[3].weight, fw.net[3].bias]
+    return ps + [m.mlp_head[0].weight, m.mlp_head[0].bias, m.mlp_head[1].weight, m.mlp_head[1].bias]
+
+
+class TokenPoseFunction(torch.autograd.Function):
+    """feature (b, c, H, W), *tokenpose_params(m) -> (b, num_keypoints, h_hm, w_hm).  Three stages of {x += MHA(LN(x));
+    x += W2 gelu(W1 LN(x))} over [keypoint tokens | patches] (one all-to-all group, no rotary tables)."""
+
+    @staticmethod
+    def forward(ctx, feature, m, prec, *params):
+        from . import hip_ops as ops
+
+        L = _lib.lib()
+        b, c, H, W = feature.shape
+        nk, dim, ps = m.num_keypoints, m.keypoint_token.shape[-1], m.patch_size[0]
+        dev = feature.device
+        tok = torch.empty(b * (H // ps) * (W // ps), ps * ps * c, dtype=torch.float32, device=dev)
+        _lib.check(L.hp_sformer_patchify(feature.data_ptr(), tok.data_ptr(), b, 1, c, H, W, ps, _st(feature)), "hp_sformer_patchify")
+        emb = linear(tok, params[0], params[1]).view(b, -1, dim)
+        n = emb.shape[1]
+        ntok = nk + n
+        pos = params[3]
+        x = torch.empty(b, ntok, dim, dtype=torch.float32, device=dev)
+        x[:, :nk] = params[2]
+        if m.pos_embedding_type in ("sine", "sine-full"):
+            x[:, nk:] = ops.add(emb.contiguous(), pos[:, :n].expand(b, -1, -1).contiguous())
+        else:
+            x[:, nk:] = emb
+            x = ops.add(x, pos[:, :n + nk].expand(b, -1, -1).contiguous())
+        del emb
+        saved, consts, outs = [], [], []
+        i = 0
+        for t in (m.transformer1, m.transformer2, m.transformer3):
+            for idx, (attn, ff) in enumerate(t.layers):
+                lp = params[4 + TP_PER_LAYER * i: 4 + TP_PER_LAYER * (i + 1)]
+                if idx > 0 and t.all_attn:   # 'sine-full': the (frozen) table re-added to the patch rows
+                    x = x.clone()
+                    x[:, nk:] = ops.add(x[:, nk:].contiguous(), pos.expand(b, -1, -1).contiguous())
+                a = attn.fn.fn
+                dh = dim // a.heads
+                x, s_a = prenorm_attention_forward(x, lp[0:5], attn.fn.norm.eps, a.scale, a.heads, dh, 0, ntok, 1, None, None, prec)
+                x, s_f = gelu_ff_forward(x, lp[5:11], ff.fn.norm.eps, prec)
+                saved += [*s_a, *s_f]
+                consts.append((a.scale, a.heads, dh, attn.fn.norm.eps, ff.fn.norm.eps))
+                i += 1
+            outs.append(x)
+        cat = torch.cat([o[:, :nk] for o in outs], dim=2).contiguous().view(b * nk, 3 * dim)
+        y = layernorm(cat, params[-4], params[-3], m.mlp_head[0].eps, b * nk, 3 * dim)
+        out = linear(y, params[-2], params[-1])
+        depths = [len(t.layers) for t in (m.transformer1, m.transformer2, m.transformer3)]
+        ctx.geom = (b, c, H, W, ps, nk, n, ntok, dim, prec, m.pos_embedding_type, m.mlp_head[0].eps, depths)
+        ctx.consts = consts
+        ctx.nsaved = len(saved)
+        ctx.save_for_backward(*saved, tok, cat, y, *params)
+        return out.view(b, nk, m.heatmap_size[0], m.heatmap_size[1])
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import hip_ops as ops
+
+        b, c, H, W, ps, nk, n, ntok, dim, prec, pe_type, eps_head, depths = ctx.geom
+        L = _lib.lib()
+        allt = ctx.saved_tensors
+        saved = allt[:ctx.nsaved]
+        tok, cat, y = allt[ctx.nsaved:ctx.nsaved + 3]
+        params = allt[ctx.nsaved + 3:]
+        dev = dout.device
+        grads = [None] * len(params)
+        dy, grads[-2], grads[-1] = linear_backward(y, dout.contiguous().view(b * nk, -1), params[-2])
+        dcat = torch.zeros(b * nk, 3 * dim, dtype=torch.float32, device=dev)
+        grads[-4], grads[-3] = layernorm_backward(cat, dy, dcat, params[-4], eps_head, b * nk, 3 * dim)
+        del dy
+        dcat = dcat.view(b, nk, 3 * dim)
+        per = 9 + 4
+        i = sum(depths)
+        dx = None
+        for s in (2, 1, 0):
+            # the stage's output gradient: what flows back from the next stage + its keypoint rows' share of the head
+            share = dcat[:, :, s * dim:(s + 1) * dim].contiguous()
+            if dx is None:
+                dx = torch.zeros(b, ntok, dim, dtype=torch.float32, device=dev)
+                dx[:, :nk] = share
+            else:
+                dx[:, :nk] = ops.add(dx[:, :nk].contiguous(), share)
+            for _ in range(depths[s]):   # ('sine-full' re-adds a frozen table: an identity on the gradient)
+                i -= 1
+                sv = saved[per * i: per * (i + 1)]
+                base = 4 + TP_PER_LAYER * i
+                lp = params[base: base + TP_PER_LAYER]
+                scale, heads, dh, e_a, e_f = ctx.consts[i]
+                grads[base + 5: base + 11] = gelu_ff_backward(dx, sv[9:13], lp[5:11], e_f, prec)
+                grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_a, scale, heads, dh, 0, ntok, 1, None, None, prec)
+        # token assembly: keypoint_token and the learnable pos_embedding are shared by the batch
+        if ctx.needs_input_grad[3 + 2]:
+            grads[2] = _joint_sum(dx, nk)
+        if pe_type == "learnable" and ctx.needs_input_grad[3 + 3]:
+            grads[3] = _joint_sum(dx, ntok)
+        demb = dx[:, nk:].contiguous().view(b * n, dim)
+        need_feat = ctx.needs_input_grad[0]
+        dtok, grads[0], grads[1] = linear_backward(tok, demb, params[0], need_dx=need_feat)
+        dfeat = None
+        if need_feat:
+            dfeat = torch.empty(b, c, H, W, dtype=torch.float32, device=dev)
+            _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dfeat.data_ptr(), b, 1, c, H, W, ps, _st(dout)), "hp_sformer_unpatchify")
+        return (dfeat, None, None, *grads)

@@ -12,6 +12,8 @@
 //   dq_patch  one thread per patch query, 64-key tiles of K and V in LDS, keys [nj joint rows of K | the frame's patches]
 //   dq_joint  the nj joint queries against all Ntok rows of K0: key splits x 8 sub-ranges per workgroup, the 8 sub-ranges
 //             summed through LDS, the splits by a merge kernel, both in index order.
+//   grouped   short groups (n <= 64, TimeSformer's time attention): dkv and dq_patch of several whole groups in one
+//             workgroup, same arithmetic and order (hp_sformer_attention_backward_grouped).
 #include <algorithm>
 #include <cfloat>
 
@@ -401,6 +403,154 @@ __global__ __launch_bounds__(SB) void k_colsum_partial(const float* __restrict__
   part[(long)blockIdx.y * cols + c] = s;
 }
 
+// Short groups (TimeSformer's time attention: n = frames of one patch position, hp*wp groups per (b, head)).  One
+// workgroup takes G whole consecutive groups of one (b, head); its patch rows are the contiguous token range
+// [nj + g0 n, nj + (g0 + G) n).  Phase 1 (thread = key, G (nj + n) threads): Q, dO, lse, delta of the G groups' patch
+// queries and of the nj joint queries staged once; a key sweeps its group's n queries (and, for a patch key or a joint key
+// of group 0, the joint queries with its K0 row), exactly as k_attn_bwd_dkv does.  Phase 2 (thread = patch query, G n
+// threads): the query keeps its q, dO, lse, delta in registers, K and V of the G groups and of the joint rows replace the
+// phase-1 images, and the query sweeps [joint keys | its group's keys] as k_attn_bwd_dq_patch does.  Joint-key partials
+// go to the per-group workspace (summed in group order by k_attn_bwd_joint_keys).  grid x = B * heads * ceil(groups / G).
+template <int DH>
+__global__ __launch_bounds__(SB) void k_attn_bwd_grouped(const float* __restrict__ Q, const float* __restrict__ K,
+                                                         const float* __restrict__ K0, const float* __restrict__ V,
+                                                         const float* __restrict__ dout, const float* __restrict__ lse,
+                                                         const float* __restrict__ delta, float* __restrict__ dQ,
+                                                         float* __restrict__ dK, float* __restrict__ dK0, float* __restrict__ dV,
+                                                         float* __restrict__ ws_dk, float* __restrict__ ws_dv, int heads, int Ntok,
+                                                         int nj, int n, int groups, int G, int wg_per_bh) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int rmax = G * n;
+  float* A = lds;                 // phase 1: Q rows of the patch queries;  phase 2: K rows of the patch keys
+  float* Bm = A + rmax * DH;      // phase 1: dO rows;                      phase 2: V rows
+  float* Ls = Bm + rmax * DH;
+  float* Ds = Ls + rmax;
+  float* Aj = Ds + rmax;          // phase 1: Q of the joint queries;       phase 2: K of the joint keys
+  float* Bj = Aj + nj * DH;       // phase 1: dO of the joint queries;      phase 2: V of the joint keys
+  float* Lj = Bj + nj * DH;
+  float* Dj = Lj + nj;
+  const int bh = blockIdx.x / wg_per_bh, g0 = (blockIdx.x % wg_per_bh) * G;
+  const int Gw = min(G, groups - g0), rows = Gw * n, per = nj + n;
+  const int b = bh / heads, head = bh % heads, inner = heads * DH;
+  const long bhN = (long)bh * Ntok;
+  const int tok0 = nj + g0 * n;
+  const float* Qb = Q + bhN * DH;
+  const float* dout_b = dout + (long)b * Ntok * inner;
+  for (int i = threadIdx.x; i < rows * DH; i += SB) {
+    const int r = i / DH, d = i - r * DH;
+    A[i] = Qb[(long)(tok0 + r) * DH + d];
+    Bm[i] = dout_b[(long)(tok0 + r) * inner + head * DH + d];
+  }
+  for (int i = threadIdx.x; i < nj * DH; i += SB) {
+    const int r = i / DH, d = i - r * DH;
+    Aj[i] = Qb[(long)r * DH + d];
+    Bj[i] = dout_b[(long)r * inner + head * DH + d];
+  }
+  for (int r = threadIdx.x; r < rows; r += SB) {
+    Ls[r] = lse[bhN + tok0 + r];
+    Ds[r] = delta[bhN + tok0 + r];
+  }
+  for (int r = threadIdx.x; r < nj; r += SB) {
+    Lj[r] = lse[bhN + r];
+    Dj[r] = delta[bhN + r];
+  }
+  __syncthreads();
+  // ---- phase 1: dK, dK0, dV
+  {
+    const int t = threadIdx.x;
+    const bool valid = t < Gw * per;
+    const int gl = valid ? t / per : 0, kj = valid ? t - gl * per : 0, g = g0 + gl;
+    const int tok = kj < nj ? kj : nj + g * n + (kj - nj);
+    float k[DH], v[DH], dk[DH], dv[DH];
+#pragma unroll
+    for (int d = 0; d < DH; ++d) {
+      k[d] = valid ? K[(bhN + tok) * DH + d] : 0.f;
+      v[d] = valid ? V[(bhN + tok) * DH + d] : 0.f;
+      dk[d] = 0.f;
+      dv[d] = 0.f;
+    }
+    if (valid)
+      for (int r = 0; r < n; ++r) {
+        const int row = gl * n + r;
+        dkv_row<DH>(A + row * DH, Bm + row * DH, Ls[row], Ds[row], k, v, dk, dv);
+      }
+    if (valid) {
+      float* dst = kj >= nj ? dK + (bhN + tok) * DH : ws_dk + (((long)bh * groups + g) * nj + kj) * DH;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) dst[d] = dk[d];
+    }
+    // a joint key takes the joint queries once (group 0); with nj = 0 every dK0 row is written as zero
+    const bool joint = valid && (kj >= nj || g == 0);
+#pragma unroll
+    for (int d = 0; d < DH; ++d) {
+      k[d] = joint ? K0[(bhN + tok) * DH + d] : 0.f;
+      dk[d] = 0.f;
+    }
+    if (joint) {
+      for (int r = 0; r < nj; ++r) dkv_row<DH>(Aj + r * DH, Bj + r * DH, Lj[r], Dj[r], k, v, dk, dv);
+#pragma unroll
+      for (int d = 0; d < DH; ++d) dK0[(bhN + tok) * DH + d] = dk[d];
+    }
+    if (valid) {
+      float* dst = kj >= nj ? dV + (bhN + tok) * DH : ws_dv + (((long)bh * groups + g) * nj + kj) * DH;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) dst[d] = dv[d];
+    }
+  }
+  // ---- phase 2: dQ of the patch queries
+  const int t = threadIdx.x;
+  const bool qvalid = t < rows;
+  const int qrow = qvalid ? t : 0;
+  float q[DH], gq[DH], dq[DH];
+#pragma unroll
+  for (int d = 0; d < DH; ++d) {
+    q[d] = A[qrow * DH + d];
+    gq[d] = Bm[qrow * DH + d];
+    dq[d] = 0.f;
+  }
+  const float Lq = Ls[qrow], Dq = Ds[qrow];
+  __syncthreads();
+  const float* Kb = K + bhN * DH;
+  const float* Vb = V + bhN * DH;
+  for (int i = threadIdx.x; i < rows * DH; i += SB) {
+    A[i] = Kb[(long)tok0 * DH + i];
+    Bm[i] = Vb[(long)tok0 * DH + i];
+  }
+  for (int i = threadIdx.x; i < nj * DH; i += SB) {
+    Aj[i] = Kb[i];
+    Bj[i] = Vb[i];
+  }
+  __syncthreads();
+  if (qvalid) {
+    const int gl = t / n;
+    for (int kj = 0; kj < per; ++kj) {
+      const float* kr = kj < nj ? Aj + kj * DH : A + (gl * n + kj - nj) * DH;
+      const float* vr = kj < nj ? Bj + kj * DH : Bm + (gl * n + kj - nj) * DH;
+      float s = 0.f, dp = 0.f;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) {
+        s = fmaf(q[d], kr[d], s);
+        dp = fmaf(gq[d], vr[d], dp);
+      }
+      const float ds = __expf(s - Lq) * (dp - Dq);
+#pragma unroll
+      for (int d = 0; d < DH; ++d) dq[d] = fmaf(ds, kr[d], dq[d]);
+    }
+#pragma unroll
+    for (int d = 0; d < DH; ++d) dQ[(bhN + tok0 + t) * DH + d] = dq[d];
+  }
+}
+
+// du = dy * gelu'(u), gelu(u) = u Phi(u): gelu'(u) = Phi(u) + u phi(u) (exact erf form); du may alias dy
+__global__ __launch_bounds__(SB) void k_gelu_bwd(const float* __restrict__ u, const float* dy, float* du, long n) {
+  for (long i = (long)blockIdx.x * SB + threadIdx.x; i < n; i += (long)gridDim.x * SB) {
+    const float t = u[i];
+    const float cdf = 0.5f * (1.0f + erff(t * 0.70710678118654752f));
+    const float pdf = 0.39894228040143268f * __expf(-0.5f * t * t);
+    du[i] = dy[i] * (cdf + t * pdf);
+  }
+}
+
 // du (rows, 2H) from dg (rows, H) and u: g = a gelu(t), gelu(t) = t Phi(t): da = dg gelu(t), dt = dg a (Phi(t) + t phi(t))
 __global__ __launch_bounds__(SB) void k_geglu_bwd(const float* __restrict__ u, const float* __restrict__ dg, float* __restrict__ du,
                                                   long rows, int Hd) {
@@ -444,6 +594,12 @@ __global__ __launch_bounds__(SB) void k_joint_token_bwd(const float* __restrict_
 
 static int ln_blocks(long rows) { return (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 1024)); }
 static int colsum_chunks(long rows) { return (int)std::max<long>(1, std::min<long>((rows + 255) / 256, 256)); }
+
+constexpr int GROUPED_MAX_N = 64;   // tokens per group of k_attn_bwd_grouped
+// LDS of k_attn_bwd_grouped: two (G n) x dh images + lse, delta of the patch rows; the same for the nj joint rows
+static size_t grouped_lds_bytes(int dh, int nj, int n, int G) {
+  return sizeof(float) * ((size_t)G * n * (2 * dh + 2) + (size_t)nj * (2 * dh + 2));
+}
 
 }  // namespace hp
 
@@ -519,6 +675,97 @@ extern "C" int hp_sformer_attention_backward(const float* Q, const float* K, con
     hipLaunchKernelGGL(k_attn_bwd_dq_joint_merge, dim3((unsigned)((total + SB - 1) / SB)), dim3(SB), 0, st, part, dQ, BH, Ntok, dh, nj,
                        nsplit);
   }
+  HP_CHECK_HIP(hipGetLastError());
+  return HP_OK;
+}
+
+// groups per workgroup of k_attn_bwd_grouped: as many whole groups as G (nj + n) <= SB threads allow, while the LDS images
+// stay within 64 KiB
+static int grouped_groups_per_wg(int dh, int nj, int n, int groups) {
+  int G = std::max(1, std::min(SB / (nj + n), groups));
+  while (G > 1 && grouped_lds_bytes(dh, nj, n, G) > 65536) --G;
+  return G;
+}
+
+extern "C" size_t hp_sformer_attention_backward_grouped_workspace_bytes(int B, int heads, int dh, int Ntok, int num_joints,
+                                                                        int groups) {
+  return hp_sformer_attention_backward_workspace_bytes(B, heads, dh, Ntok, num_joints, groups);
+}
+
+extern "C" int hp_sformer_attention_backward_grouped(const float* Q, const float* K, const float* K0, const float* V,
+                                                     const float* out, const float* dout, const float* lse, float* dQ, float* dK,
+                                                     float* dK0, float* dV, int B, int heads, int dh, int Ntok, int num_joints,
+                                                     int patches_per_group, int groups, void* workspace, size_t workspace_bytes,
+                                                     void* stream) {
+  HP_REQUIRE(Q && K && K0 && V && out && dout && lse && dQ && dK && dK0 && dV && workspace,
+             "hp_sformer_attention_backward_grouped: null argument");
+  HP_REQUIRE(B > 0 && heads > 0 && groups > 0 && patches_per_group > 0 && num_joints >= 0 && num_joints <= 32 &&
+                 Ntok == num_joints + groups * patches_per_group,
+             "hp_sformer_attention_backward_grouped: bad token layout");
+  if (dh != 16 && dh != 24 && dh != 32) {
+    set_error("hp_sformer_attention_backward_grouped: dim_head %d not built (16, 24, 32)", dh);
+    return HP_ERR_UNSUPPORTED;
+  }
+  if (patches_per_group > GROUPED_MAX_N) {
+    set_error("hp_sformer_attention_backward_grouped: %d tokens per group not built (at most %d; use hp_sformer_attention_backward)",
+              patches_per_group, GROUPED_MAX_N);
+    return HP_ERR_UNSUPPORTED;
+  }
+  if (workspace_bytes < hp_sformer_attention_backward_grouped_workspace_bytes(B, heads, dh, Ntok, num_joints, groups)) {
+    set_error("hp_sformer_attention_backward_grouped: workspace too small");
+    return HP_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int BH = B * heads, nj = num_joints, n = patches_per_group;
+  float* delta = (float*)workspace;
+  float* ws_dk = delta + (size_t)BH * Ntok;
+  float* ws_dv = ws_dk + (size_t)BH * groups * nj * dh;
+  float* part = ws_dv + (size_t)BH * groups * nj * dh;
+  const int G = grouped_groups_per_wg(dh, nj, n, groups);
+  const int wg_per_bh = (groups + G - 1) / G;
+  const long nwg = (long)BH * wg_per_bh;
+  HP_REQUIRE(nwg < (1l << 31), "hp_sformer_attention_backward_grouped: grid too large");
+  const size_t lds = grouped_lds_bytes(dh, nj, n, G);
+  {
+    HP_PROF("sformer_attn_bwd_delta", st);
+    hipLaunchKernelGGL(k_attn_bwd_delta, dim3(bgrid((long)BH * Ntok)), dim3(SB), 0, st, out, dout, delta, B, heads, dh, Ntok);
+  }
+  {
+    HP_PROF("sformer_attn_bwd_grouped", st);
+#define HP_GRP(D) hipLaunchKernelGGL((k_attn_bwd_grouped<D>), dim3((unsigned)nwg), dim3(SB), lds, st, Q, K, K0, V, dout, lse, delta, dQ, dK, dK0, dV, ws_dk, ws_dv, heads, Ntok, nj, n, groups, G, wg_per_bh)
+    if (dh == 32) HP_GRP(32);
+    else if (dh == 24) HP_GRP(24);
+    else HP_GRP(16);
+#undef HP_GRP
+  }
+  if (nj > 0) {
+    HP_PROF("sformer_attn_bwd_joint_keys", st);
+    const long total = (long)BH * nj * dh;
+    hipLaunchKernelGGL(k_attn_bwd_joint_keys, dim3((unsigned)((total + SB - 1) / SB)), dim3(SB), 0, st, ws_dk, ws_dv, dK, dV, BH, Ntok, dh,
+                       nj, groups);
+  }
+  if (nj > 0) {
+    HP_PROF("sformer_attn_bwd_dq_joint", st);
+    const int nsplit = std::max(1, std::min(DQ_SPLITS, (Ntok + 255) / 256));
+    const dim3 gj(nsplit, BH);
+#define HP_DQJ(D) hipLaunchKernelGGL((k_attn_bwd_dq_joint<D>), gj, dim3(SB), 0, st, Q, K0, V, dout, lse, delta, part, heads, Ntok, nj)
+    if (dh == 32) HP_DQJ(32);
+    else if (dh == 24) HP_DQJ(24);
+    else HP_DQJ(16);
+#undef HP_DQJ
+    const long total = (long)BH * nj * dh;
+    hipLaunchKernelGGL(k_attn_bwd_dq_joint_merge, dim3((unsigned)((total + SB - 1) / SB)), dim3(SB), 0, st, part, dQ, BH, Ntok, dh, nj,
+                       nsplit);
+  }
+  HP_CHECK_HIP(hipGetLastError());
+  return HP_OK;
+}
+
+extern "C" int hp_gelu_backward(const float* u, const float* dy, float* du, long n, void* stream) {
+  HP_REQUIRE(u && dy && du && n > 0, "hp_gelu_backward: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  HP_PROF("gelu_bwd", st);
+  hipLaunchKernelGGL(k_gelu_bwd, dim3(bgrid(n)), dim3(SB), 0, st, u, dy, du, n);
   HP_CHECK_HIP(hipGetLastError());
   return HP_OK;
 }

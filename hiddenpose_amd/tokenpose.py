@@ -1,11 +1,12 @@
 """TokenPose-L: keypoint tokens + patch tokens through three stacked vanilla transformers, heat-map MLP head.
 
-Drop-in (inference) for models/tokenpose.py `TokenPose_L_base(**kwargs)` (:66-227) and `TokenPose_L(cfg)` (:30-63):
+Drop-in for models/tokenpose.py `TokenPose_L_base(**kwargs)` (:66-227) and `TokenPose_L(cfg)` (:30-63):
 same constructor keywords, same state_dict keys, `forward(feature (b, c, H, W)) -> (b, num_keypoints, h_hm, w_hm)`.
 Patchify 'b c (h p1)(w p2) -> b (h w)(p1 p2 c)' -> Linear -> [keypoint tokens | patches] (+ position embedding;
 'sine-full' re-adds it to the patch tokens before every layer but the first, :311-313) -> 3 x Transformer(depth) of
 {x += MHA(LN(x)); x += W2 gelu(W1 LN(x))} -> concat of the keypoint tokens of the three stages -> LayerNorm + Linear
-(+ LayerNorm + Linear) -> heat-maps.  All arithmetic in libhiddenpose_hip.so (_xformer.py); `mask` is not supported."""
+(+ LayerNorm + Linear) -> heat-maps.  All arithmetic in libhiddenpose_hip.so (_xformer.py); trainable through
+_xformer_autograd.TokenPoseFunction (a HIP backward).  `mask` is not supported."""
 from __future__ import annotations
 
 import math
@@ -15,6 +16,7 @@ from torch import nn
 
 from . import _lib
 from . import _xformer as X
+from . import _xformer_autograd as _xa
 from . import hip_ops as ops
 
 
@@ -89,6 +91,7 @@ class TokenPose_L_base(nn.Module):
         self.num_patches = h * w
         self.patch_size, self.heatmap_size, self.num_keypoints = list(patch_size), list(heatmap_size), num_keypoints
         self.pos_embedding_type = pos_embedding_type
+        self.dropout, self.emb_dropout = dropout, emb_dropout
         self.all_attn = pos_embedding_type == "sine-full"
         self.keypoint_token = nn.Parameter(torch.zeros(1, num_keypoints, dim))
         if pos_embedding_type == "learnable":
@@ -120,11 +123,25 @@ class TokenPose_L_base(nn.Module):
         pos_y = torch.stack((pos_y[:, :, :, 0::2].sin(), pos_y[:, :, :, 1::2].cos()), dim=4).flatten(3)
         return torch.cat((pos_y, pos_x), dim=3).permute(0, 3, 1, 2).flatten(2).permute(0, 2, 1).contiguous()
 
-    @torch.no_grad()
     def forward(self, feature, mask=None):
+        """An autograd graph (_xformer_autograd.TokenPoseFunction) is built when grad mode is on, the module is in training
+        mode or `feature` requires grad, and something (a parameter or `feature`) requires grad.  Its forward runs the same
+        kernels in the same order as the no-graph path (the output is bit-identical); training needs dropout 0.  Otherwise
+        the no-graph path runs, launch for launch as an inference-only module would."""
         assert mask is None, "masks are not supported"
         if not feature.is_cuda:
             raise _lib.HiddenPoseHipError("TokenPose.forward needs a tensor on a HIP device; there is no CPU path")
+        params = _xa.tokenpose_params(self)
+        if (torch.is_grad_enabled() and (self.training or feature.requires_grad)
+                and (feature.requires_grad or any(p.requires_grad for p in params))):
+            if self.dropout > 0 or self.emb_dropout > 0:
+                raise _lib.HiddenPoseHipError("TokenPose training: dropout is not built (dropout / emb_dropout must be 0)")
+            with torch.cuda.device(feature.device):
+                return _xa.TokenPoseFunction.apply(feature.contiguous().float(), self, X.PREC[self.linear_precision], *params)
+        with torch.no_grad():
+            return self._forward_nograd(feature)
+
+    def _forward_nograd(self, feature):
         feature = feature.contiguous().float()
         b, c, H, W = feature.shape
         nk, dim = self.num_keypoints, self.keypoint_token.shape[-1]

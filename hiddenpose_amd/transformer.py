@@ -1,12 +1,13 @@
 """TimeSformer: divided space-time attention with one class token, axial / temporal rotary embeddings, GEGLU
 feed-forward and optional token shift.
 
-Drop-in (inference) for models/transformer.py `TimeSformer(**kwargs)` (:152-257): same constructor keywords, same
+Drop-in for models/transformer.py `TimeSformer(**kwargs)` (:152-257): same constructor keywords, same
 state_dict keys, `forward(video (b, f, c, H, W)) -> (b, 72)`.  Per layer (:251-254): x += TimeAttn(LN(x)) over the f
 tokens that share a patch position; x += SpaceAttn(LN(x)) over the n patches of a frame; x += GEGLU-FF(LN(x)).  In
 both attentions the class token attends to all tokens with un-rotated keys, the patch tokens to [class | their group]
 (:110-141).  All arithmetic is in libhiddenpose_hip.so (see _xformer.py); the '(b n) f' regrouping of the time
-attention is a transposed copy of the token matrix.  `mask` (frame masks for ragged clips) is not supported."""
+attention is a transposed copy of the token matrix.  Trainable: autograd runs _xformer_autograd.TimeSformerFunction, whose
+backward is a chain of HIP kernels (csrc/sformer_backward.hip).  `mask` (frame masks for ragged clips) is not supported."""
 from __future__ import annotations
 
 from math import log, pi
@@ -16,6 +17,7 @@ from torch import nn
 
 from . import _lib
 from . import _xformer as X
+from . import _xformer_autograd as _xa
 from .NlosPoseSformer import AxialRotaryEmbedding, RotaryEmbedding, _Attention, _FeedForward, _PreNorm
 
 
@@ -53,6 +55,7 @@ class TimeSformer(nn.Module):
         assert rotary_emb, "only the rotary-embedding variant is built"
         _lib.lib()
         self.heads, self.dim_head, self.patch_size, self.num_frames, self.shift_tokens = heads, dim_head, patch_size, num_frames, shift_tokens
+        self.attn_dropout, self.ff_dropout = attn_dropout, ff_dropout
         self.to_patch_embedding = nn.Linear(channels * patch_size ** 2, dim)
         self.cls_token = nn.Parameter(torch.randn(1, dim))
         self.frame_rot_emb = RotaryEmbedding(dim_head)
@@ -68,11 +71,25 @@ class TimeSformer(nn.Module):
         freqs = torch.cat((freqs, freqs), dim=-1).contiguous()     # models/rotary.py:57-61
         return freqs.sin().contiguous(), freqs.cos().contiguous()
 
-    @torch.no_grad()
     def forward(self, video, mask=None):
+        """An autograd graph (_xformer_autograd.TimeSformerFunction) is built when grad mode is on, the module is in
+        training mode or `video` requires grad, and something (a parameter or `video`) requires grad.  Its forward runs the
+        same kernels in the same order as the no-graph path (the output is bit-identical); training needs dropout 0.
+        Otherwise the no-graph path runs, launch for launch as an inference-only module would."""
         assert mask is None, "frame masks are not supported"
         if not video.is_cuda:
             raise _lib.HiddenPoseHipError("TimeSformer.forward needs a tensor on a HIP device; there is no CPU path")
+        params = _xa.timesformer_params(self)
+        if (torch.is_grad_enabled() and (self.training or video.requires_grad)
+                and (video.requires_grad or any(p.requires_grad for p in params))):
+            if self.attn_dropout > 0 or self.ff_dropout > 0:
+                raise _lib.HiddenPoseHipError("TimeSformer training: dropout is not built (attn_dropout / ff_dropout must be 0)")
+            with torch.cuda.device(video.device):
+                return _xa.TimeSformerFunction.apply(video.contiguous().float(), self, X.PREC[self.linear_precision], *params)
+        with torch.no_grad():
+            return self._forward_nograd(video)
+
+    def _forward_nograd(self, video):
         video = video.contiguous().float()
         b, f, c, H, W = video.shape
         ps, heads, dh = self.patch_size, self.heads, self.dim_head

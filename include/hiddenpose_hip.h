@@ -466,7 +466,7 @@ int hp_sformer_attention(const float* Q, const float* K, const float* K0, const 
                          void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------
- * NlosPoseSformer backward (training path of NlosPoseSformer.forward).  Every reduction runs in a fixed order: two calls
+ * NlosPoseSformer backward (training path of NlosPoseSformer.forward; TimeSformer and TokenPose-L use it too).  Every reduction runs in a fixed order: two calls
  * on the same inputs give identical outputs, except the Linear weight gradient (the convolution weight gradient's split
  * reduction meets in fp32 atomics).
  * ---------------------------------------------------------------------- */
@@ -485,6 +485,17 @@ int hp_sformer_attention_backward(const float* Q, const float* K, const float* K
                                   const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B,
                                   int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
                                   void* workspace, size_t workspace_bytes, void* stream);
+/* hp_sformer_attention_backward for short groups (TimeSformer's time attention on the transposed token grid: groups =
+ * hp*wp patch positions of patches_per_group = frames tokens).  Same arguments, layout Ntok = num_joints + groups *
+ * patches_per_group, outputs and reduction order (joint-key partials summed in group order, joint-query dQ split and merged
+ * in index order); one workgroup takes as many whole groups as fit, grid x = B * heads * workgroups per (b, head).  Exact fp32,
+ * no float atomics.  patches_per_group <= 64, 0 <= num_joints <= 32, dh 16 / 24 / 32; another patches_per_group or dh returns
+ * HP_ERR_UNSUPPORTED. */
+size_t hp_sformer_attention_backward_grouped_workspace_bytes(int B, int heads, int dh, int Ntok, int num_joints, int groups);
+int hp_sformer_attention_backward_grouped(const float* Q, const float* K, const float* K0, const float* V, const float* out,
+                                          const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B,
+                                          int heads, int dh, int Ntok, int num_joints, int patches_per_group, int groups,
+                                          void* workspace, size_t workspace_bytes, void* stream);
 /* Transpose of hp_sformer_qkv_prepare: dqkv (B, Ntok, 3 * heads * dh) = [scale R^T(dQ) | R^T(dK) + dK0 | dV], R^T the
  * inverse rotation on the patch tokens' first rot_dim dims (identity on the joint tokens). */
 int hp_sformer_qkv_prepare_backward(const float* dQ, const float* dK, const float* dK0, const float* dV, float* dqkv, int B,
@@ -499,6 +510,9 @@ int hp_layernorm_backward(const float* x, const float* dy, float* dx, float* dga
                           size_t workspace_bytes, void* stream);
 /* GEGLU backward: du (rows, 2 hidden) from the GEMM output u (rows, 2 hidden) and dg (rows, hidden), exact erf GELU. */
 int hp_geglu_backward(const float* u, const float* dg, float* du, long rows, int hidden, void* stream);
+/* GELU backward (nn.GELU(), exact erf form, the derivative of hp_gelu_forward): du = dy * gelu'(u) over n values; du may
+ * alias dy. */
+int hp_gelu_backward(const float* u, const float* dy, float* du, long n, void* stream);
 /* nn.Linear data gradient dx (M, K) = dy (M, N) @ w (N, K) [+ addend] (addend may be NULL, must not be dx): the 1x1x1
  * convolution data gradient with its packed weight image built into the workspace.  precision as the forward's. */
 size_t hp_linear_backward_data_workspace_bytes(int K, int N);

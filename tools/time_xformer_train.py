@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""TimeSformer and TokenPose-L training-step timing (fp32, seeded inputs): per head the no-graph forward, graph-mode forward,
+backward, whole step, the library's per-kernel profile of one step and the peak device memory; the A/B of the time
+attention's backward (hp_sformer_attention_backward_grouped against the generic hp_sformer_attention_backward, same saved
+inputs, same process, median of the timed calls); the device's maxGridSize; and whether the no-graph TimeSformer forward
+(time attention grid y = B * heads * hp * wp) launches at batch 8.  One JSON line.
+
+    python tools/time_xformer_train.py [--steps 5] [--warmup 2] [--ab-calls 20]
+
+TimeSformer: dim 256, depth 8, 8 heads x 32, 16 frames of 128^2, patch 4, 1 channel, batch 4.
+TokenPose-L: the models/token_config.py geometry (dim 192, 3 x depth 2, 8 heads x 24, 16 keypoints, 4 x 4 patches of a
+128-channel 64^2 map, 64^2 heat-maps, sine-full), batch 8.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from hiddenpose_amd import _lib  # noqa: E402
+from hiddenpose_amd import _xformer_autograd as xa  # noqa: E402
+from hiddenpose_amd import testing as hpt  # noqa: E402
+from hiddenpose_amd.tokenpose import TokenPose_L_base  # noqa: E402
+from hiddenpose_amd.transformer import TimeSformer  # noqa: E402
+
+TS_KW = dict(dim=256, num_frames=16, num_classes=10, image_size=128, patch_size=4, channels=1, depth=8, heads=8, dim_head=32)
+TP_KW = dict(feature_size=[64, 64], patch_size=[4, 4], num_keypoints=16, dim=192, depth=2, heads=8, mlp_dim=576, heatmap_dim=4096,
+             heatmap_size=[64, 64], channels=128, pos_embedding_type="sine-full", hidden_heatmap_dim=384)
+
+
+def timed(fn, steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def head_timing(m, x, R, steps, warmup):
+    m = m.cuda()
+
+    def fwd_nograd():
+        with torch.no_grad():
+            m.eval()(x)
+
+    state = {}
+
+    def fwd_graph():
+        state["y"] = m.train()(x)
+
+    def step():
+        y = m.train()(x)
+        m.zero_grad(set_to_none=True)
+        (y * R).sum().backward()
+
+    for _ in range(warmup):
+        fwd_nograd()
+        step()
+    t_nograd = timed(fwd_nograd, steps)
+    t_graph = timed(fwd_graph, steps)
+    state.clear()
+    t_step = timed(step, steps)
+    torch.cuda.reset_peak_memory_stats()
+    step()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated()
+    _lib.profile_enable(True)
+    _lib.profile_reset()
+    step()
+    torch.cuda.synchronize()
+    prof = _lib.profile_read()
+    _lib.profile_enable(False)
+    return {
+        "forward_nograd_ms": round(t_nograd, 2), "forward_graph_ms": round(t_graph, 2), "backward_ms": round(t_step - t_graph, 2),
+        "step_ms": round(t_step, 2), "step_over_nograd_forward": round(t_step / t_nograd, 2), "peak_memory_gb": round(peak / 1e9, 2),
+        "kernels_ms": {k: [cnt, round(ms, 3)] for k, (cnt, ms) in sorted(prof.items(), key=lambda kv: -kv[1][1])},
+    }
+
+
+def time_attention_ab(m, B, calls):
+    """Time attention's backward of layer 0 on saved inputs of a real forward: grouped vs generic entry."""
+    f, hp = TS_KW["num_frames"], TS_KW["image_size"] // TS_KW["patch_size"]
+    n, heads, dh, dim = hp * hp, m.heads, m.dim_head, TS_KW["dim"]
+    ntok = 1 + f * n
+    g = torch.Generator().manual_seed(7)
+    x = torch.randn(B, ntok, dim, generator=g).cuda()
+    time_attn = m.layers[0][0]
+    p = (time_attn.norm.weight, time_attn.norm.bias, time_attn.fn.to_qkv.weight, time_attn.fn.to_out[0].weight, time_attn.fn.to_out[0].bias)
+    sin_t, cos_t = m._frame_tables(f, x.device)
+    with torch.no_grad():
+        _, sv = xa.prenorm_attention_forward(x, p, time_attn.norm.eps, time_attn.fn.scale, heads, dh, 1, f, n, sin_t, cos_t, 0,
+                                             perm=lambda t: xa.time_perm(t, f, n), unperm=lambda t: xa.time_unperm(t, f, n))
+    _x, _h, q, k, k0, v, att, lse, _ab = sv
+    datt = torch.randn(B, ntok, heads * dh, generator=g).cuda()
+    res = {}
+    outs = {}
+    for name, fn, args in (("grouped", xa.attention_backward_grouped, (1, f, n)), ("generic", xa.attention_backward, (1, f, n))):
+        for _ in range(3):
+            outs[name] = fn(q, k, k0, v, att, datt, lse, B, heads, dh, ntok, *args)
+        ts = []
+        for _ in range(calls):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn(q, k, k0, v, att, datt, lse, B, heads, dh, ntok, *args)
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        res[name + "_ms"] = round(statistics.median(ts), 3)
+    res["grouped_over_generic"] = round(res["grouped_ms"] / res["generic_ms"], 3)
+    res["bit_equal"] = [bool(torch.equal(a, b)) for a, b in zip(outs["grouped"], outs["generic"])]
+    res["geometry"] = {"batch": B, "heads": heads, "dh": dh, "groups": n, "tokens_per_group": f, "num_joints": 1}
+    return res
+
+
+def max_grid_size():
+    hip = ctypes.CDLL("libamdhip64.so")
+    dev = torch.cuda.current_device()
+    out = []
+    for attr in (29, 30, 31):   # hipDeviceAttributeMaxGridDimX / Y / Z (hip_runtime_api.h)
+        v = ctypes.c_int(0)
+        rc = hip.hipDeviceGetAttribute(ctypes.byref(v), attr, dev)
+        out.append(v.value if rc == 0 else None)
+    return out
+
+
+def forward_batch8_launches(m):
+    """The no-graph forward at batch 8 (time attention grid y = 8 * 8 * 1024 = 65536) against two batch-4 halves."""
+    video = torch.rand(8, 16, 1, 128, 128, generator=torch.Generator().manual_seed(9)).cuda()
+    try:
+        with torch.no_grad():
+            y = m.eval()(video)
+            y4 = torch.cat((m(video[:4]), m(video[4:])))
+        torch.cuda.synchronize()
+        return {"launches": True, "equals_two_batch4_halves": bool(torch.equal(y, y4))}
+    except _lib.HiddenPoseHipError as e:
+        return {"launches": False, "error": str(e)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--ab-calls", type=int, default=20)
+    a = ap.parse_args()
+    out = {"precision": "fp32", "time_attention_backward": xa.TIME_ATTENTION_BACKWARD, "max_grid_size": max_grid_size()}
+    ts = TimeSformer(**TS_KW)
+    hpt.fill_module(ts, "timesformer.")
+    ts = ts.cuda()
+    out["timesformer_time_attention_backward_ab"] = time_attention_ab(ts, 4, a.ab_calls)
+    video = torch.rand(4, 16, 1, 128, 128, generator=torch.Generator().manual_seed(5)).cuda()
+    R = torch.randn(4, 72, generator=torch.Generator().manual_seed(6)).cuda()
+    out["timesformer"] = {"batch": 4, "depth": 8, **head_timing(ts, video, R, a.steps, a.warmup)}
+    del video, R
+    torch.cuda.empty_cache()
+    tp = TokenPose_L_base(**TP_KW)
+    hpt.fill_module(tp, "tokenpose.")
+    feat = torch.rand(8, 128, 64, 64, generator=torch.Generator().manual_seed(5)).cuda()
+    R = torch.randn(8, 16, 64, 64, generator=torch.Generator().manual_seed(6)).cuda()
+    out["tokenpose_l"] = {"batch": 8, **head_timing(tp, feat, R, a.steps, a.warmup)}
+    del tp, feat, R
+    torch.cuda.empty_cache()
+    out["timesformer_forward_batch8"] = forward_batch8_launches(ts)   # last: a refused launch ends nothing else
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
