@@ -81,7 +81,7 @@ class NlosPoseSformer(nn.Module):
     # arithmetic of the transformer-layer Linear GEMMs: "fp32" (exact, default) or the bf16 matrix-core modes of
     # hp_conv_desc.precision; attention, LayerNorm, GEGLU, patch embedding and the output head stay fp32
     linear_precision = "fp32"
-    # patch-token attention: "fp32" (exact-fp32 MFMA, default), "bf16" or "fp16" (16-bit matrix cores, fp32 soft-max; dim_head 32)
+    # patch-token attention: "fp32" (exact-fp32 MFMA, default), "bf16" or "fp16" (16-bit matrix cores, fp32 soft-max; dim_head 32 or 64)
     attention_precision = "fp32"
 
     def __init__(self, *, dim, num_frames, num_joints=24, image_size=224, patch_size=16, channels=2, depth=12, heads=8,
@@ -118,8 +118,8 @@ class NlosPoseSformer(nn.Module):
             if self.attn_dropout > 0 or self.ff_dropout > 0:
                 raise _lib.HiddenPoseHipError("NlosPoseSformer training: dropout is not built (attn_dropout / ff_dropout must be 0)")
             aprec = {"fp32": 0, "bf16": 1, "fp16": 4}[self.attention_precision]
-            if aprec and self.dim_head != 32:
-                raise _lib.HiddenPoseHipError("bf16 / fp16 attention is built for dim_head 32 only")
+            if aprec and self.dim_head not in (32, 64):
+                raise _lib.HiddenPoseHipError("bf16 / fp16 attention is built for dim_head 32 and 64 only")
             with torch.cuda.device(video.device):
                 return _xa.SformerFunction.apply(video.contiguous().float(), self, _LINEAR_PRECISION[self.linear_precision], aprec,
                                                  *params)
@@ -139,8 +139,8 @@ class NlosPoseSformer(nn.Module):
         st = _lib.current_stream_handle(dev)
         prec = _LINEAR_PRECISION[self.linear_precision]
         aprec = {"fp32": 0, "bf16": 1, "fp16": 4}[self.attention_precision]
-        if aprec and dh != 32:
-            raise _lib.HiddenPoseHipError("bf16 / fp16 attention is built for dim_head 32 only")
+        if aprec and dh not in (32, 64):
+            raise _lib.HiddenPoseHipError("bf16 / fp16 attention is built for dim_head 32 and 64 only")
         with torch.cuda.device(dev):
             tokens = torch.empty(b * f * n, ps * ps * c, dtype=torch.float32, device=dev)
             _lib.check(L.hp_sformer_patchify(video.data_ptr(), tokens.data_ptr(), b, f, c, H, W, ps, st), "hp_sformer_patchify")

@@ -267,6 +267,7 @@ def attention_backward_grouped(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, 
 # time attention's backward: "grouped" (hp_sformer_attention_backward_grouped) or "generic" (hp_sformer_attention_backward);
 # DESIGN 4.4.2 records the A/B that chose it
 TIME_ATTENTION_BACKWARD = "grouped"
+GROUPED_DIM_HEADS = (16, 24, 32)   # the grouped entry is not built for dim_head 64: that width takes the generic one
 
 
 def time_perm(t, f, n):
@@ -531,7 +532,7 @@ class TimeSformerFunction(torch.autograd.Function):
         del dcls
         pre_adj = (lambda t: token_shift_adjoint(t, f)) if shift else None
         perm, unperm = (lambda t: time_perm(t, f, n)), (lambda t: time_unperm(t, f, n))
-        grouped = TIME_ATTENTION_BACKWARD == "grouped"
+        grouped = TIME_ATTENTION_BACKWARD == "grouped" and dh in GROUPED_DIM_HEADS
         per = 9 + 9 + 3
         for i in reversed(range(len(ctx.consts))):
             sv = saved[per * i: per * (i + 1)]

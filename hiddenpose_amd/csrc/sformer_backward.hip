@@ -14,6 +14,7 @@
 //             summed through LDS, the splits by a merge kernel, both in index order.
 //   grouped   short groups (n <= 64, TimeSformer's time attention): dkv and dq_patch of several whole groups in one
 //             workgroup, same arithmetic and order (hp_sformer_attention_backward_grouped).
+//   dh 64     dkv, dq_patch and dq_joint with the key / query on a lane PAIR, 32 values of d per lane (k_attn_bwd_*64 below).
 #include <algorithm>
 #include <cfloat>
 
@@ -291,6 +292,250 @@ __global__ __launch_bounds__(SB) void k_attn_bwd_dq_joint_merge(const float* __r
   float s = 0.f;
   for (int sp = 0; sp < nsplit; ++sp) s += part[((bh * nsplit + sp) * 32 + j) * dh + d];
   dQ[(bh * Ntok + j) * dh + d] = s;
+}
+
+// ---- dim_head 64: d split over a lane pair ---------------------------------------------------------------------------------
+// The key-per-thread form would hold k, v, dk, dv = 4 x 64 floats per thread at this width and spill.  Here a key (dkv) or a
+// query (dq) belongs to the lane PAIR (2i, 2i + 1): lane hf of the pair holds d = 32 hf .. 32 hf + 31 of every row it keeps, so
+// the register set is the one of the dh-32 kernels.  The two 32-term halves of a dot product meet in one xor-1 exchange (a DPP
+// quad permute: VALU, no trip through the LDS crossbar as ds_bpermute would take in the middle of a dependent chain); a + b and
+// b + a are the same float, so both lanes go on with identical s, dp, p and ds.  A workgroup takes 128 keys or queries; the LDS
+// tiles, the sweep order, the joint-key partials and the joint-query splits are unchanged.
+constexpr int HD = 32;       // d per lane
+constexpr int PB = SB / 2;   // keys / queries per workgroup
+
+// x + (x of the other lane of the pair); quad_perm [1, 0, 3, 2].  Both lanes of a pair are always active together.
+__device__ __forceinline__ float pair_sum(float x) {
+  return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true));
+}
+
+__device__ __forceinline__ void dkv_row_pair(const float* q, const float* g, float lse, float delta, const float (&k)[HD],
+                                             const float (&v)[HD], float (&dk)[HD], float (&dv)[HD]) {
+  float s = 0.f, dp = 0.f;
+#pragma unroll
+  for (int d = 0; d < HD; ++d) {
+    s = fmaf(k[d], q[d], s);
+    dp = fmaf(v[d], g[d], dp);
+  }
+  s = pair_sum(s);
+  dp = pair_sum(dp);
+  const float p = __expf(s - lse);
+  const float ds = p * (dp - delta);
+#pragma unroll
+  for (int d = 0; d < HD; ++d) {
+    dv[d] = fmaf(p, g[d], dv[d]);
+    dk[d] = fmaf(ds, q[d], dk[d]);
+  }
+}
+
+// grid (ceil((nj + n) / PB), B * heads * frames); k_attn_bwd_dkv with the key on a lane pair
+__global__ __launch_bounds__(SB) void k_attn_bwd_dkv64(const float* __restrict__ Q, const float* __restrict__ K,
+                                                       const float* __restrict__ K0, const float* __restrict__ V,
+                                                       const float* __restrict__ dout, const float* __restrict__ lse,
+                                                       const float* __restrict__ delta, float* __restrict__ dK,
+                                                       float* __restrict__ dK0, float* __restrict__ dV,
+                                                       float* __restrict__ ws_dk, float* __restrict__ ws_dv, int heads, int Ntok,
+                                                       int nj, int n, int frames) {
+  constexpr int DH = 64;
+  __shared__ __attribute__((aligned(16))) float Qs[QT * DH];
+  __shared__ __attribute__((aligned(16))) float Gs[QT * DH];
+  __shared__ float Ls[QT], Ds[QT];
+  const int bh = blockIdx.y / frames, f = blockIdx.y % frames;
+  const int b = bh / heads, head = bh % heads, inner = heads * DH;
+  const int hf = threadIdx.x & 1, d0 = hf * HD;
+  const int kj = blockIdx.x * PB + (threadIdx.x >> 1);
+  const bool valid = kj < nj + n;
+  const int tok = kj < nj ? kj : nj + f * n + (kj - nj);
+  const long bhN = (long)bh * Ntok;
+  const float* Qb = Q + bhN * DH;
+  const float* dout_b = dout + (long)b * Ntok * inner;
+  const float* lse_b = lse + bhN;
+  const float* delta_b = delta + bhN;
+  float k[HD], v[HD], dk[HD], dv[HD];
+#pragma unroll
+  for (int d = 0; d < HD; ++d) {
+    k[d] = valid ? K[(bhN + tok) * DH + d0 + d] : 0.f;
+    v[d] = valid ? V[(bhN + tok) * DH + d0 + d] : 0.f;
+    dk[d] = 0.f;
+    dv[d] = 0.f;
+  }
+  // the frame's n patch queries
+  for (int q0 = 0; q0 < n; q0 += QT) {
+    const int rows = min(QT, n - q0);
+    __syncthreads();
+    stage_queries<DH>(Qs, Gs, Ls, Ds, Qb, dout_b, lse_b, delta_b, inner, head, nj + f * n + q0, rows);
+    __syncthreads();
+    for (int r = 0; r < rows; ++r) dkv_row_pair(Qs + r * DH + d0, Gs + r * DH + d0, Ls[r], Ds[r], k, v, dk, dv);
+  }
+  // patch-query part of dK: a patch key's own row, or this frame's partial of a joint key
+  if (valid) {
+    float* dst = (kj >= nj ? dK + (bhN + tok) * DH : ws_dk + (((long)bh * frames + f) * nj + kj) * DH) + d0;
+#pragma unroll
+    for (int d = 0; d < HD; ++d) dst[d] = dk[d];
+  }
+  // the nj joint queries attend to the keys BEFORE the rotary embedding (K0); a joint key takes them once (frame 0)
+  const bool joint = valid && (kj >= nj || f == 0);
+#pragma unroll
+  for (int d = 0; d < HD; ++d) {
+    k[d] = joint ? K0[(bhN + tok) * DH + d0 + d] : 0.f;
+    dk[d] = 0.f;
+  }
+  if (nj > 0) {
+    __syncthreads();
+    stage_queries<DH>(Qs, Gs, Ls, Ds, Qb, dout_b, lse_b, delta_b, inner, head, 0, nj);
+    __syncthreads();
+    if (joint)   // (both lanes of a pair share kj: the exchange inside never crosses this branch)
+      for (int r = 0; r < nj; ++r) dkv_row_pair(Qs + r * DH + d0, Gs + r * DH + d0, Ls[r], Ds[r], k, v, dk, dv);
+  }
+  if (joint) {
+#pragma unroll
+    for (int d = 0; d < HD; ++d) dK0[(bhN + tok) * DH + d0 + d] = dk[d];
+  }
+  if (valid) {
+    float* dst = (kj >= nj ? dV + (bhN + tok) * DH : ws_dv + (((long)bh * frames + f) * nj + kj) * DH) + d0;
+#pragma unroll
+    for (int d = 0; d < HD; ++d) dst[d] = dv[d];
+  }
+}
+
+// grid (ceil(n / PB), B * heads * frames): k_attn_bwd_dq_patch with the query on a lane pair
+__global__ __launch_bounds__(SB) void k_attn_bwd_dq_patch64(const float* __restrict__ Q, const float* __restrict__ K,
+                                                            const float* __restrict__ V, const float* __restrict__ dout,
+                                                            const float* __restrict__ lse, const float* __restrict__ delta,
+                                                            float* __restrict__ dQ, int heads, int Ntok, int nj, int n, int frames) {
+  constexpr int DH = 64;
+  __shared__ __attribute__((aligned(16))) float Ks[KT * DH];
+  __shared__ __attribute__((aligned(16))) float Vs[KT * DH];
+  const int bh = blockIdx.y / frames, f = blockIdx.y % frames;
+  const int b = bh / heads, head = bh % heads, inner = heads * DH;
+  const int hf = threadIdx.x & 1, d0 = hf * HD;
+  const int qi = blockIdx.x * PB + (threadIdx.x >> 1);
+  const bool valid = qi < n;
+  const int tok = nj + f * n + min(qi, n - 1);
+  const long bhN = (long)bh * Ntok;
+  float q[HD], g[HD], dq[HD];
+#pragma unroll
+  for (int d = 0; d < HD; ++d) {
+    q[d] = Q[(bhN + tok) * DH + d0 + d];
+    g[d] = dout[((long)b * Ntok + tok) * inner + head * DH + d0 + d];
+    dq[d] = 0.f;
+  }
+  const float L = lse[bhN + tok], Dl = delta[bhN + tok];
+  const int nkeys = nj + n;
+  for (int k0 = 0; k0 < nkeys; k0 += KT) {
+    const int rows = min(KT, nkeys - k0);
+    __syncthreads();
+    // 64 rows x 16 float4 of K and of V: four of each per thread, all eight loads in flight before the first LDS store (a tile
+    // is twice the bytes of the dh-32 kernel's for half the queries)
+    float4 kq[4], vq[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int i = threadIdx.x + u * SB, r = i / (DH / 4), d = (i - r * (DH / 4)) * 4;
+      const int kj = k0 + r;
+      kq[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      vq[u] = kq[u];
+      if (r < rows) {
+        const int kt = kj < nj ? kj : nj + f * n + (kj - nj);
+        kq[u] = *(const float4*)(K + (bhN + kt) * DH + d);
+        vq[u] = *(const float4*)(V + (bhN + kt) * DH + d);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int i = threadIdx.x + u * SB;
+      *(float4*)(Ks + 4 * i) = kq[u];
+      *(float4*)(Vs + 4 * i) = vq[u];
+    }
+    __syncthreads();
+    for (int r = 0; r < rows; ++r) {
+      // The K half-row is read ONCE, as eight 16-byte reads, and kept for the dQ update.  The two lanes of a pair read rows
+      // 128 bytes apart: the same bank under the 32-bank rule of the 4- and 8-byte LDS reads (a 2-way conflict the dh-32
+      // kernel, whose wave reads one address, never has), distinct banks under the 64-bank rule of ds_read_b128.
+      const float4* kr = (const float4*)(Ks + r * DH + d0);
+      const float4* vr = (const float4*)(Vs + r * DH + d0);
+      float4 kk[HD / 4];
+      float s = 0.f, dp = 0.f;
+#pragma unroll
+      for (int u = 0; u < HD / 4; ++u) {
+        kk[u] = kr[u];
+        const float4 vv = vr[u];
+        s = fmaf(q[4 * u + 0], kk[u].x, s);
+        s = fmaf(q[4 * u + 1], kk[u].y, s);
+        s = fmaf(q[4 * u + 2], kk[u].z, s);
+        s = fmaf(q[4 * u + 3], kk[u].w, s);
+        dp = fmaf(g[4 * u + 0], vv.x, dp);
+        dp = fmaf(g[4 * u + 1], vv.y, dp);
+        dp = fmaf(g[4 * u + 2], vv.z, dp);
+        dp = fmaf(g[4 * u + 3], vv.w, dp);
+      }
+      s = pair_sum(s);
+      dp = pair_sum(dp);
+      const float ds = __expf(s - L) * (dp - Dl);
+#pragma unroll
+      for (int u = 0; u < HD / 4; ++u) {
+        dq[4 * u + 0] = fmaf(ds, kk[u].x, dq[4 * u + 0]);
+        dq[4 * u + 1] = fmaf(ds, kk[u].y, dq[4 * u + 1]);
+        dq[4 * u + 2] = fmaf(ds, kk[u].z, dq[4 * u + 2]);
+        dq[4 * u + 3] = fmaf(ds, kk[u].w, dq[4 * u + 3]);
+      }
+    }
+  }
+  if (valid) {
+#pragma unroll
+    for (int d = 0; d < HD; ++d) dQ[(bhN + tok) * DH + d0 + d] = dq[d];
+  }
+}
+
+// grid (nsplit, B * heads): k_attn_bwd_dq_joint with the query on a lane pair.  Thread = (d half tid & 1, query (tid >> 1) & 31,
+// sub-range tid >> 6); sub-range s takes the split's keys s, s + 4, s + 8, ...; the 4 sub-ranges are summed through LDS in order.
+__global__ __launch_bounds__(SB) void k_attn_bwd_dq_joint64(const float* __restrict__ Q, const float* __restrict__ K0,
+                                                            const float* __restrict__ V, const float* __restrict__ dout,
+                                                            const float* __restrict__ lse, const float* __restrict__ delta,
+                                                            float* __restrict__ part, int heads, int Ntok, int nj) {
+  constexpr int DH = 64;
+  __shared__ float red[4][32][DH + 1];
+  const int bh = blockIdx.y, b = bh / heads, head = bh % heads, inner = heads * DH;
+  const int hf = threadIdx.x & 1, d0 = hf * HD, qr = (threadIdx.x >> 1) & 31, sub = threadIdx.x >> 6;
+  const int nsplit = gridDim.x, per = (Ntok + nsplit - 1) / nsplit;
+  const int kbeg = blockIdx.x * per, kend = min(Ntok, kbeg + per);
+  const long bhN = (long)bh * Ntok;
+  float dq[HD];
+#pragma unroll
+  for (int d = 0; d < HD; ++d) dq[d] = 0.f;
+  if (qr < nj) {
+    float q[HD], g[HD];
+#pragma unroll
+    for (int d = 0; d < HD; ++d) {
+      q[d] = Q[(bhN + qr) * DH + d0 + d];
+      g[d] = dout[((long)b * Ntok + qr) * inner + head * DH + d0 + d];
+    }
+    const float L = lse[bhN + qr], Dl = delta[bhN + qr];
+    for (int kj = kbeg + sub; kj < kend; kj += 4) {
+      const float* kr = K0 + (bhN + kj) * DH + d0;
+      const float* vr = V + (bhN + kj) * DH + d0;
+      float s = 0.f, dp = 0.f;
+#pragma unroll
+      for (int d = 0; d < HD; ++d) {
+        s = fmaf(q[d], kr[d], s);
+        dp = fmaf(g[d], vr[d], dp);
+      }
+      s = pair_sum(s);
+      dp = pair_sum(dp);
+      const float ds = __expf(s - L) * (dp - Dl);
+#pragma unroll
+      for (int d = 0; d < HD; ++d) dq[d] = fmaf(ds, kr[d], dq[d]);
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < HD; ++d) red[sub][qr][d0 + d] = dq[d];
+  __syncthreads();
+  float* rec = part + ((long)bh * nsplit + blockIdx.x) * 32 * DH;
+  for (int i = threadIdx.x; i < 32 * DH; i += SB) {
+    const int r = i / DH, d = i - r * DH;
+    float s = 0.f;
+    for (int u = 0; u < 4; ++u) s += red[u][r][d];
+    rec[i] = s;
+  }
 }
 
 // Transpose of k_qkv_prepare: dQ, dK, dK0, dV (B, heads, Ntok, dh) -> dqkv (B, Ntok, 3 inner).
@@ -621,8 +866,8 @@ extern "C" int hp_sformer_attention_backward(const float* Q, const float* K, con
   HP_REQUIRE(B > 0 && heads > 0 && frames > 0 && patches_per_frame > 0 && num_joints >= 0 && num_joints <= 32 &&
                  Ntok == num_joints + frames * patches_per_frame,
              "hp_sformer_attention_backward: bad token layout");
-  if (dh != 16 && dh != 24 && dh != 32) {
-    set_error("hp_sformer_attention_backward: dim_head %d not built (16, 24, 32)", dh);
+  if (dh != 16 && dh != 24 && dh != 32 && dh != 64) {
+    set_error("hp_sformer_attention_backward: dim_head %d not built (16, 24, 32, 64)", dh);
     return HP_ERR_UNSUPPORTED;
   }
   if (workspace_bytes < hp_sformer_attention_backward_workspace_bytes(B, heads, dh, Ntok, num_joints, frames)) {
@@ -640,10 +885,14 @@ extern "C" int hp_sformer_attention_backward(const float* Q, const float* K, con
     hipLaunchKernelGGL(k_attn_bwd_delta, dim3(bgrid((long)BH * Ntok)), dim3(SB), 0, st, out, dout, delta, B, heads, dh, Ntok);
   }
   const dim3 gkv((nj + n + SB - 1) / SB, BH * frames), gq((n + SB - 1) / SB, BH * frames);
+  const dim3 gkv64((nj + n + PB - 1) / PB, BH * frames), gq64((n + PB - 1) / PB, BH * frames);   // dh 64: a lane pair per key / query
   {
     HP_PROF("sformer_attn_bwd_dkv", st);
 #define HP_DKV(D) hipLaunchKernelGGL((k_attn_bwd_dkv<D>), gkv, dim3(SB), 0, st, Q, K, K0, V, dout, lse, delta, dK, dK0, dV, ws_dk, ws_dv, heads, Ntok, nj, n, frames)
-    if (dh == 32) HP_DKV(32);
+    if (dh == 64)
+      hipLaunchKernelGGL(k_attn_bwd_dkv64, gkv64, dim3(SB), 0, st, Q, K, K0, V, dout, lse, delta, dK, dK0, dV, ws_dk, ws_dv, heads, Ntok, nj, n,
+                         frames);
+    else if (dh == 32) HP_DKV(32);
     else if (dh == 24) HP_DKV(24);
     else HP_DKV(16);
 #undef HP_DKV
@@ -657,7 +906,8 @@ extern "C" int hp_sformer_attention_backward(const float* Q, const float* K, con
   {
     HP_PROF("sformer_attn_bwd_dq", st);
 #define HP_DQ(D) hipLaunchKernelGGL((k_attn_bwd_dq_patch<D>), gq, dim3(SB), 0, st, Q, K, V, dout, lse, delta, dQ, heads, Ntok, nj, n, frames)
-    if (dh == 32) HP_DQ(32);
+    if (dh == 64) hipLaunchKernelGGL(k_attn_bwd_dq_patch64, gq64, dim3(SB), 0, st, Q, K, V, dout, lse, delta, dQ, heads, Ntok, nj, n, frames);
+    else if (dh == 32) HP_DQ(32);
     else if (dh == 24) HP_DQ(24);
     else HP_DQ(16);
 #undef HP_DQ
@@ -667,7 +917,8 @@ extern "C" int hp_sformer_attention_backward(const float* Q, const float* K, con
     const int nsplit = std::max(1, std::min(DQ_SPLITS, (Ntok + 255) / 256));
     const dim3 gj(nsplit, BH);
 #define HP_DQJ(D) hipLaunchKernelGGL((k_attn_bwd_dq_joint<D>), gj, dim3(SB), 0, st, Q, K0, V, dout, lse, delta, part, heads, Ntok, nj)
-    if (dh == 32) HP_DQJ(32);
+    if (dh == 64) hipLaunchKernelGGL(k_attn_bwd_dq_joint64, gj, dim3(SB), 0, st, Q, K0, V, dout, lse, delta, part, heads, Ntok, nj);
+    else if (dh == 32) HP_DQJ(32);
     else if (dh == 24) HP_DQJ(24);
     else HP_DQJ(16);
 #undef HP_DQJ

@@ -461,6 +461,339 @@ __global__ void k_attention_joint_merge(const float* __restrict__ part, float* _
   if (lse && d == 0) lse[(long)bh * Ntok + qr] = M + logf(L);
 }
 
+// ---- dim_head 64 (the constructors' default width) ----------------------------------------------------------------------
+// k_attention at DH = 64: same grid, modes, key order and partial records; what changes with the width:
+//   O^T [d][query] is TWO 32x32 accumulators (d 0..31 and 32..63), so every P register feeds two P.V MFMAs;
+//   the K tiles keep the odd row stride (65 floats: the A-operand reads of 32 keys fall on distinct banks), the V tile
+//   is read with the lane running along d, so its rows stay 64 floats and are staged and kept as float4;
+//   four per-wave K + V tile pairs would need 66.5 KB, over the 64 KB a workgroup may declare: in joint mode only K goes
+//   through LDS (per wave, as before) and the V^T operand is read from global memory, 128 contiguous bytes per
+//   (key, accumulator) and wave.  LDS 42.5 KB: three workgroups per CU.
+template <bool LSE = false>
+__global__ __launch_bounds__(ST) void k_attention64(const float* __restrict__ Q, const float* __restrict__ K,
+                                                    const float* __restrict__ V, float* __restrict__ out, int heads,
+                                                    int Ntok, int nj, int n, int frames, int mode,
+                                                    float* __restrict__ part, float* __restrict__ lse = nullptr) {
+  constexpr int DH = 64, LD = DH + 1;
+  __shared__ float Ks[4][32 * LD];
+  __shared__ __attribute__((aligned(16))) float Vs[32 * DH];   // patch mode: the workgroup's V tile
+  __shared__ float mrg_m[4][32], mrg_l[4][32];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  int bh, f = 0;
+  if (mode == 0) {
+    bh = blockIdx.y / frames;
+    f = blockIdx.y % frames;
+  } else {
+    bh = blockIdx.y;
+  }
+  const int b = bh / heads, head = bh % heads;
+  const float* Qb = Q + (long)bh * Ntok * DH;
+  const float* Kb = K + (long)bh * Ntok * DH;
+  const float* Vb = V + (long)bh * Ntok * DH;
+  const int nkeys = mode == 0 ? nj + n : Ntok;
+  const int nq = mode == 0 ? n : nj;
+  const int qi = mode == 0 ? blockIdx.x * 128 + wave * 32 + col : col;
+  const bool qvalid = qi < nq;
+  const int qtok = mode == 0 ? nj + f * n + qi : qi;
+  float qreg[DH / 2];
+#pragma unroll
+  for (int s = 0; s < DH / 2; ++s) qreg[s] = qvalid ? Qb[(long)qtok * DH + 2 * s + half] : 0.f;
+
+  f32x16 oacc0, oacc1;   // O^T rows d = 0..31 and 32..63
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    oacc0[r] = 0.f;
+    oacc1[r] = 0.f;
+  }
+  float m = -FLT_MAX, l = 0.f;
+
+  const int ntiles = (nkeys + 31) / 32;
+  const int nsplit = mode == 0 ? 1 : (int)gridDim.x;
+  const int tiles_per_split = (ntiles + nsplit - 1) / nsplit;
+  const int tile0 = mode == 0 ? 0 : (int)blockIdx.x * tiles_per_split;
+  const int tile_end = mode == 0 ? ntiles : min(ntiles, tile0 + tiles_per_split);
+  const int steps = mode == 0 ? ntiles : (tiles_per_split + 3) / 4;
+  for (int it = 0; it < steps; ++it) {
+    const int tile = mode == 0 ? it : tile0 + it * 4 + wave;
+    __syncthreads();
+    if (mode == 0) {  // one tile for the whole block: 32 keys x 16 float4 of K and of V, two of each per thread
+      for (int i = tid; i < 32 * (DH / 4); i += ST) {
+        const int kr = i / (DH / 4), d = (i - kr * (DH / 4)) * 4;
+        const int kj = tile * 32 + kr;
+        float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
+        if (kj < nkeys) {
+          const int tok = kj < nj ? kj : nj + f * n + (kj - nj);
+          kv = *(const float4*)(Kb + (long)tok * DH + d);
+          vv = *(const float4*)(Vb + (long)tok * DH + d);
+        }
+        float* kd = Ks[0] + kr * LD + d;
+        kd[0] = kv.x;
+        kd[1] = kv.y;
+        kd[2] = kv.z;
+        kd[3] = kv.w;
+        *(float4*)(Vs + kr * DH + d) = vv;
+      }
+    } else {  // every wave stages the K rows of its own tile
+      for (int i = lane; i < 32 * (DH / 4); i += 64) {
+        const int kr = i / (DH / 4), d = (i - kr * (DH / 4)) * 4;
+        const int kj = tile * 32 + kr;
+        float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (kj < nkeys && tile < tile_end) kv = *(const float4*)(Kb + (long)kj * DH + d);
+        float* kd = Ks[wave] + kr * LD + d;
+        kd[0] = kv.x;
+        kd[1] = kv.y;
+        kd[2] = kv.z;
+        kd[3] = kv.w;
+      }
+    }
+    __syncthreads();
+    const float* ks = mode == 0 ? Ks[0] : Ks[wave];
+    if (tile >= tile_end) continue;  // (joint mode tail; barriers above stay uniform)
+    f32x16 sacc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < DH / 2; ++s) sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(ks[col * LD + 2 * s + half], qreg[s], sacc, 0, 0, 0);
+    float tm = -FLT_MAX;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+      if (key >= nkeys) sacc[r] = -FLT_MAX;
+      tm = fmaxf(tm, sacc[r]);
+    }
+    tm = fmaxf(tm, __shfl_xor(tm, 32));
+    const float mn = fmaxf(m, tm);
+    const float alpha = __expf(m - mn);
+    float ps = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float pr = sacc[r] > -FLT_MAX ? __expf(sacc[r] - mn) : 0.f;
+      sacc[r] = pr;
+      ps += pr;
+    }
+    ps += __shfl_xor(ps, 32);
+    l = l * alpha + ps;
+    m = mn;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      oacc0[r] *= alpha;
+      oacc1[r] *= alpha;
+    }
+    // O^T[d][query] += V^T[d][key] P[key][query], k order = accumulator row order of P; d = col and 32 + col
+    if (mode == 0) {
+#pragma unroll
+      for (int s = 0; s < 16; ++s) {
+        const int key = (s & 3) + 8 * (s >> 2) + 4 * half;
+        oacc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[key * DH + col], sacc[s], oacc0, 0, 0, 0);
+        oacc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[key * DH + 32 + col], sacc[s], oacc1, 0, 0, 0);
+      }
+    } else {
+      float va[16], vb[16];
+#pragma unroll
+      for (int s = 0; s < 16; ++s) {
+        const int kj = tile * 32 + (s & 3) + 8 * (s >> 2) + 4 * half;
+        va[s] = kj < nkeys ? Vb[(long)kj * DH + col] : 0.f;
+        vb[s] = kj < nkeys ? Vb[(long)kj * DH + 32 + col] : 0.f;
+      }
+#pragma unroll
+      for (int s = 0; s < 16; ++s) {
+        oacc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(va[s], sacc[s], oacc0, 0, 0, 0);
+        oacc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vb[s], sacc[s], oacc1, 0, 0, 0);
+      }
+    }
+  }
+
+  const int inner = heads * DH;
+  __syncthreads();
+  float* os = Ks[wave];  // [32 queries][LD]; every K region is free now
+  if (mode == 0) {
+    // normalise, transpose through LDS and store 256-byte rows
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int d = (r & 3) + 8 * (r >> 2) + 4 * half;
+      os[col * LD + d] = oacc0[r] * inv;
+      os[col * LD + 32 + d] = oacc1[r] * inv;
+    }
+    if (LSE && qvalid && half == 0) lse[(long)bh * Ntok + qtok] = m + logf(l);
+    __syncthreads();
+    for (int i = lane; i < 32 * DH; i += 64) {
+      const int qr = i / DH, d = i - qr * DH;
+      const int q2 = blockIdx.x * 128 + wave * 32 + qr;
+      if (q2 < nq) out[((long)b * Ntok + nj + f * n + q2) * inner + head * DH + d] = os[qr * LD + d];
+    }
+  } else {
+    // merge the 4 waves' partial results for the same 32 queries
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int d = (r & 3) + 8 * (r >> 2) + 4 * half;
+      os[col * LD + d] = oacc0[r];
+      os[col * LD + 32 + d] = oacc1[r];
+    }
+    if (half == 0) {
+      mrg_m[wave][col] = m;
+      mrg_l[wave][col] = l;
+    }
+    __syncthreads();
+    float* rec = part + ((long)blockIdx.y * nsplit + blockIdx.x) * (32 * (DH + 2));
+    for (int i = tid; i < 32 * DH; i += ST) {
+      const int qr = i / DH, d = i - qr * DH;
+      float M = -FLT_MAX;
+      for (int w = 0; w < 4; ++w) M = fmaxf(M, mrg_m[w][qr]);
+      float Lsum = 0.f, o = 0.f;
+      for (int w = 0; w < 4; ++w) {
+        const float sc = mrg_l[w][qr] > 0.f ? __expf(mrg_m[w][qr] - M) : 0.f;
+        Lsum += mrg_l[w][qr] * sc;
+        o += Ks[w][qr * LD + d] * sc;
+      }
+      rec[qr * (DH + 2) + d] = o;
+      if (d == 0) {
+        rec[qr * (DH + 2) + DH] = M;
+        rec[qr * (DH + 2) + DH + 1] = Lsum;
+      }
+    }
+  }
+}
+
+// k_attention_patch_h16 at DH = 64: the same dataflow (log2-domain scores, P consumed as it lies in the accumulator,
+// the next tile's rows requested before the current tile's arithmetic).  Per 32-key tile: 4 MFMAs for S^T (k = d in four
+// steps of 16) and 2 x 2 for the two O^T accumulators, against the same 512 exp2 per wave as at 32: twice the matrix
+// work per unit of soft-max work.  K rows are 72 halves (144 bytes), V^T is [64 d][32 key slots + 8].
+template <typename H>
+__global__ __launch_bounds__(ST) void k_attention_patch_h16_64(const float* __restrict__ Q, const float* __restrict__ K,
+                                                                const float* __restrict__ V, float* __restrict__ out, int heads,
+                                                                int Ntok, int nj, int n, int frames) {
+  constexpr int DH = 64, LDB = DH + 8, LDV = 32 + 8;
+  using bf16x8s = __attribute__((ext_vector_type(8))) H;
+  __shared__ __attribute__((aligned(16))) H Kh[32 * LDB];   // [key][d]
+  __shared__ __attribute__((aligned(16))) H Vt[DH * LDV];   // [d][key slot]
+  __shared__ float os[4][32 * (DH + 1)];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  const int bh = blockIdx.y / frames, f = blockIdx.y % frames;
+  const int b = bh / heads, head = bh % heads;
+  const float* Qb = Q + (long)bh * Ntok * DH;
+  const float* Kb = K + (long)bh * Ntok * DH;
+  const float* Vb = V + (long)bh * Ntok * DH;
+  const int nkeys = nj + n;
+  const int qi = blockIdx.x * 128 + wave * 32 + col;
+  // B operand of S^T: this lane's query, d = 16 s + 8 half .. + 7, carrying log2 e
+  constexpr float LOG2E = 1.4426950408889634f;
+  bf16x8s qf[4];
+  {
+    const float* qrow = Qb + (long)(nj + f * n + min(qi, n - 1)) * DH + 8 * half;
+    float4 q4[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) q4[u] = *(const float4*)(qrow + 16 * (u >> 1) + 4 * (u & 1));
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      qf[u >> 1][4 * (u & 1) + 0] = (H)(q4[u].x * LOG2E);
+      qf[u >> 1][4 * (u & 1) + 1] = (H)(q4[u].y * LOG2E);
+      qf[u >> 1][4 * (u & 1) + 2] = (H)(q4[u].z * LOG2E);
+      qf[u >> 1][4 * (u & 1) + 3] = (H)(q4[u].w * LOG2E);
+    }
+  }
+
+  f32x16 oacc0, oacc1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    oacc0[r] = 0.f;
+    oacc1[r] = 0.f;
+  }
+  float m = -FLT_MAX, l = 0.f;
+  const int ntiles = (nkeys + 31) / 32;
+  typedef __attribute__((ext_vector_type(4))) H h4;
+  // 32 keys x 16 channel quads: two float4 of K and of V per thread (keys kr and kr + 16, the same channel quad)
+  const int kr = tid >> 4, dq = (tid & 15) * 4;
+  auto slot_of = [](int k) { return (k >> 4) * 16 + ((k >> 2) & 1) * 8 + (k & 3) + 4 * ((k >> 3) & 1); };
+  const int slot0 = slot_of(kr), slot1 = slot_of(kr + 16);
+  auto request = [&](int tile, float4 (&kv)[2], float4 (&vv)[2]) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int kj = min(tile * 32 + kr + 16 * u, nkeys - 1);   // rows past the last key: any finite row (their scores are masked)
+      const int tok = kj < nj ? kj : nj + f * n + (kj - nj);
+      kv[u] = *(const float4*)(Kb + (long)tok * DH + dq);
+      vv[u] = *(const float4*)(Vb + (long)tok * DH + dq);
+    }
+  };
+  float4 kv[2], vv[2];
+  request(0, kv, vv);
+  for (int tile = 0; tile < ntiles; ++tile) {
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int slot = u ? slot1 : slot0;
+      *(h4*)(Kh + (kr + 16 * u) * LDB + dq) = (h4){(H)kv[u].x, (H)kv[u].y, (H)kv[u].z, (H)kv[u].w};
+      Vt[(dq + 0) * LDV + slot] = (H)vv[u].x;
+      Vt[(dq + 1) * LDV + slot] = (H)vv[u].y;
+      Vt[(dq + 2) * LDV + slot] = (H)vv[u].z;
+      Vt[(dq + 3) * LDV + slot] = (H)vv[u].w;
+    }
+    if (tile + 1 < ntiles) request(tile + 1, kv, vv);
+    __syncthreads();
+    f32x16 sacc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
+#pragma unroll
+    for (int s2 = 0; s2 < 4; ++s2)
+      sacc = mfma_h16<H>(*(const bf16x8s*)(Kh + col * LDB + 16 * s2 + 8 * half), qf[s2], sacc);
+    const bool ragged = tile == ntiles - 1 && (nkeys & 31) != 0;   // workgroup-uniform
+    if (ragged) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (key >= nkeys) sacc[r] = -FLT_MAX;
+      }
+    }
+    float tm = fmaxf(fmaxf(fmaxf(sacc[0], sacc[1]), fmaxf(sacc[2], sacc[3])), fmaxf(fmaxf(sacc[4], sacc[5]), fmaxf(sacc[6], sacc[7])));
+    tm = fmaxf(tm, fmaxf(fmaxf(fmaxf(sacc[8], sacc[9]), fmaxf(sacc[10], sacc[11])), fmaxf(fmaxf(sacc[12], sacc[13]), fmaxf(sacc[14], sacc[15]))));
+    tm = fmaxf(tm, __shfl_xor(tm, 32));
+    if (__builtin_amdgcn_ballot_w64(tm > m) != 0ull) {   // some query of this wave has a new maximum: rescale
+      const float mn = fmaxf(m, tm);
+      const float alpha = __builtin_amdgcn_exp2f(m - mn);
+      l *= alpha;
+      m = mn;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        oacc0[r] *= alpha;
+        oacc1[r] *= alpha;
+      }
+    }
+    float ps = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float pr = __builtin_amdgcn_exp2f(sacc[r] - m);   // masked keys: exp2(-huge) = 0
+      sacc[r] = pr;
+      ps += pr;
+    }
+    ps += __shfl_xor(ps, 32);
+    l += ps;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      bf16x8s pf;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pf[j] = (H)sacc[8 * t + j];
+      oacc0 = mfma_h16<H>(*(const bf16x8s*)(Vt + col * LDV + 16 * t + 8 * half), pf, oacc0);
+      oacc1 = mfma_h16<H>(*(const bf16x8s*)(Vt + (32 + col) * LDV + 16 * t + 8 * half), pf, oacc1);
+    }
+  }
+  // normalise, transpose through LDS and store 256-byte rows
+  const int inner = heads * DH;
+  float* o = os[wave];
+  const float inv = l > 0.f ? 1.0f / l : 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int d = (r & 3) + 8 * (r >> 2) + 4 * half;
+    o[col * (DH + 1) + d] = oacc0[r] * inv;
+    o[col * (DH + 1) + 32 + d] = oacc1[r] * inv;
+  }
+  __syncthreads();
+  for (int i = lane; i < 32 * DH; i += 64) {
+    const int qr = i / DH, d = i - qr * DH;
+    const int q2 = blockIdx.x * 128 + wave * 32 + qr;
+    if (q2 < n) out[((long)b * Ntok + nj + f * n + q2) * inner + head * DH + d] = o[qr * (DH + 1) + d];
+  }
+}
+
 static unsigned sgrid(long n) { return (unsigned)std::max<long>(1, std::min<long>((n + ST - 1) / ST, 256 * 8)); }
 
 }  // namespace hp
@@ -534,9 +867,10 @@ extern "C" int hp_sformer_attention(const float* Q, const float* K, const float*
   HP_REQUIRE(num_joints <= 32 && Ntok == num_joints + frames * patches_per_frame, "hp_sformer_attention: bad token layout");
   HP_REQUIRE(precision == HP_PRECISION_FP32 || precision == HP_PRECISION_BF16 || precision == HP_PRECISION_FP16,
              "hp_sformer_attention: precision %d not built", precision);
-  HP_REQUIRE(precision == HP_PRECISION_FP32 || dh == 32, "hp_sformer_attention: the 16-bit patch attention is built for dim_head 32");
-  if (dh != 16 && dh != 24 && dh != 32) {
-    set_error("hp_sformer_attention: dim_head %d not built (16, 24, 32)", dh);
+  HP_REQUIRE(precision == HP_PRECISION_FP32 || dh == 32 || dh == 64,
+             "hp_sformer_attention: the 16-bit patch attention is built for dim_head 32 and 64");
+  if (dh != 16 && dh != 24 && dh != 32 && dh != 64) {
+    set_error("hp_sformer_attention: dim_head %d not built (16, 24, 32, 64)", dh);
     return HP_ERR_UNSUPPORTED;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -546,7 +880,14 @@ extern "C" int hp_sformer_attention(const float* Q, const float* K, const float*
   const dim3 gp((patches_per_frame + 127) / 128, B * heads * frames), gj(nsplit, B * heads);
   {
     HP_PROF("sformer_attention_patch", st);
-    if (dh == 32 && precision == HP_PRECISION_BF16)
+    if (dh == 64 && precision == HP_PRECISION_BF16)
+      hipLaunchKernelGGL(k_attention_patch_h16_64<__bf16>, gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame,
+                         frames);
+    else if (dh == 64 && precision == HP_PRECISION_FP16)
+      hipLaunchKernelGGL(k_attention_patch_h16_64<_Float16>, gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame,
+                         frames);
+    else if (dh == 64) hipLaunchKernelGGL((k_attention64<false>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 0, part, (float*)nullptr);
+    else if (dh == 32 && precision == HP_PRECISION_BF16)
       hipLaunchKernelGGL(k_attention_patch_h16<__bf16>, gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame,
                          frames);
     else if (dh == 32 && precision == HP_PRECISION_FP16)
@@ -558,7 +899,8 @@ extern "C" int hp_sformer_attention(const float* Q, const float* K, const float*
   }
   if (num_joints > 0) {  // (TokenPose's all-to-all attention has no separate joint / class queries)
     HP_PROF("sformer_attention_joint", st);
-    if (dh == 32) hipLaunchKernelGGL((k_attention<32>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part);
+    if (dh == 64) hipLaunchKernelGGL((k_attention64<false>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, (float*)nullptr);
+    else if (dh == 32) hipLaunchKernelGGL((k_attention<32>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part);
     else if (dh == 24) hipLaunchKernelGGL((k_attention<24>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part);
     else hipLaunchKernelGGL((k_attention<16>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part);
     const int total = B * heads * num_joints * dh;
@@ -576,8 +918,8 @@ extern "C" int hp_sformer_attention_lse(const float* Q, const float* K, const fl
                                         void* stream) {
   HP_REQUIRE(Q && K && K0 && V && out && lse && workspace, "hp_sformer_attention_lse: null argument");
   HP_REQUIRE(num_joints <= 32 && Ntok == num_joints + frames * patches_per_frame, "hp_sformer_attention_lse: bad token layout");
-  if (dh != 16 && dh != 24 && dh != 32) {
-    set_error("hp_sformer_attention_lse: dim_head %d not built (16, 24, 32)", dh);
+  if (dh != 16 && dh != 24 && dh != 32 && dh != 64) {
+    set_error("hp_sformer_attention_lse: dim_head %d not built (16, 24, 32, 64)", dh);
     return HP_ERR_UNSUPPORTED;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -587,13 +929,15 @@ extern "C" int hp_sformer_attention_lse(const float* Q, const float* K, const fl
   const dim3 gp((patches_per_frame + 127) / 128, B * heads * frames), gj(nsplit, B * heads);
   {
     HP_PROF("sformer_attention_patch", st);
-    if (dh == 32) hipLaunchKernelGGL((k_attention<32, true>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 0, part, lse);
+    if (dh == 64) hipLaunchKernelGGL((k_attention64<true>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 0, part, lse);
+    else if (dh == 32) hipLaunchKernelGGL((k_attention<32, true>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 0, part, lse);
     else if (dh == 24) hipLaunchKernelGGL((k_attention<24, true>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 0, part, lse);
     else hipLaunchKernelGGL((k_attention<16, true>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 0, part, lse);
   }
   if (num_joints > 0) {
     HP_PROF("sformer_attention_joint", st);
-    if (dh == 32) hipLaunchKernelGGL((k_attention<32>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
+    if (dh == 64) hipLaunchKernelGGL((k_attention64<false>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, (float*)nullptr);
+    else if (dh == 32) hipLaunchKernelGGL((k_attention<32>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
     else if (dh == 24) hipLaunchKernelGGL((k_attention<24>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
     else hipLaunchKernelGGL((k_attention<16>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
     const int total = B * heads * num_joints * dh;

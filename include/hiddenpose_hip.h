@@ -451,15 +451,19 @@ int hp_gelu_forward(const float* x, float* y, long n, void* stream);
 /* GEGLU (:197-201): g = u[:, :hidden] * gelu(u[:, hidden:]) with the exact (erf) GELU */
 int hp_geglu_forward(const float* u, float* g, long rows, int hidden, void* stream);
 /* chunk(3) + 'b n (h d) -> (b h) n d' + q * scale + axial RoPE on the patch tokens (:160-172, :298-313).
- * K0 receives the keys WITHOUT the rotary embedding: the joint queries attend before it is applied (:305). */
+ * K0 receives the keys WITHOUT the rotary embedding: the joint queries attend before it is applied (:305).  Any dh with
+ * rot_dim <= dh (the axial table of a 64-wide head is 64 wide). */
 int hp_sformer_qkv_prepare(const float* qkv, float* Q, float* K, float* K0, float* V, int B, int Ntok, int heads, int dh,
                            int num_joints, int patches_per_frame, float scale, const float* sin_t, const float* cos_t,
                            int rot_dim, void* stream);
 /* spatial attention with joint tokens (:284-319): joint queries attend to all tokens, patch queries to
- * [joint tokens | patches of their frame]; out (B, Ntok, heads*dh) with heads merged. */
+ * [joint tokens | patches of their frame]; out (B, Ntok, heads*dh) with heads merged.  dh 16 / 24 / 32 / 64 (64 is the
+ * modules' default dim_head); another dh returns HP_ERR_UNSUPPORTED.  The 16-bit kernels and every dh-64 kernel read the
+ * rows of Q, K, V 16 bytes at a time: their base addresses must be 16-byte aligned.  The workspace holds the joint queries'
+ * partial records: 32 key splits x 32 queries x (dh + 2) floats per (b, head). */
 size_t hp_sformer_attention_workspace_bytes(int B, int heads, int dh);
 /* precision: HP_PRECISION_FP32 (exact-fp32 MFMA), HP_PRECISION_BF16 or HP_PRECISION_FP16 (patch-token attention with
- * bf16 / fp16 operands on the 16-bit matrix cores, fp32 soft-max and accumulation, dim_head 32; the 24 joint queries stay
+ * bf16 / fp16 operands on the 16-bit matrix cores, fp32 soft-max and accumulation, dim_head 32 or 64; the joint queries stay
  * fp32).  HP_PRECISION_FP16 is BASELINE configs[4]'s "MFMA fp16 attention" (models/NlosPoseSformer.py:284-319). */
 int hp_sformer_attention(const float* Q, const float* K, const float* K0, const float* V, float* out, int B, int heads,
                          int dh, int Ntok, int num_joints, int patches_per_frame, int frames, int precision,
@@ -472,14 +476,16 @@ int hp_sformer_attention(const float* Q, const float* K, const float* K0, const 
  * ---------------------------------------------------------------------- */
 /* hp_sformer_attention in fp32 (same workspace) that also writes lse (B, heads, Ntok): the natural-log sum of exp of every
  * query's scores over its own key set (patch queries: [joint tokens | their frame]; joint queries: all tokens), on the
- * pre-scaled scores.  `out` is bit-identical to hp_sformer_attention(..., HP_PRECISION_FP32, ...). */
+ * pre-scaled scores.  `out` is bit-identical to hp_sformer_attention(..., HP_PRECISION_FP32, ...).  dh 16 / 24 / 32 / 64. */
 int hp_sformer_attention_lse(const float* Q, const float* K, const float* K0, const float* V, float* out, float* lse, int B,
                              int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames, void* workspace,
                              void* stream);
 /* Gradients dQ, dK, dK0, dV (B, heads, Ntok, dh) of the fp32 attention from Q, K, K0, V, its output `out` and lse and the
  * incoming gradient dout (both in the merged (B, Ntok, heads * dh) layout).  dK0 is the gradient through the joint
- * queries' keys (K0); dK the one through the patch queries' keys (RoPE on patch rows).  Exact fp32, dh 16 / 24 / 32,
- * 0 <= num_joints <= 32. */
+ * queries' keys (K0); dK the one through the patch queries' keys (RoPE on patch rows).  Exact fp32, no float atomics,
+ * dh 16 / 24 / 32 / 64 (at 64 a key or a query is held by a lane pair, 32 values of d on each lane), 0 <= num_joints <= 32;
+ * another dh returns HP_ERR_UNSUPPORTED.  The workspace (delta, the joint keys' per-frame partials, the joint queries' split
+ * partials) is sized by the function below for every one of these dh. */
 size_t hp_sformer_attention_backward_workspace_bytes(int B, int heads, int dh, int Ntok, int num_joints, int frames);
 int hp_sformer_attention_backward(const float* Q, const float* K, const float* K0, const float* V, const float* out,
                                   const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B,
@@ -489,8 +495,8 @@ int hp_sformer_attention_backward(const float* Q, const float* K, const float* K
  * hp*wp patch positions of patches_per_group = frames tokens).  Same arguments, layout Ntok = num_joints + groups *
  * patches_per_group, outputs and reduction order (joint-key partials summed in group order, joint-query dQ split and merged
  * in index order); one workgroup takes as many whole groups as fit, grid x = B * heads * workgroups per (b, head).  Exact fp32,
- * no float atomics.  patches_per_group <= 64, 0 <= num_joints <= 32, dh 16 / 24 / 32; another patches_per_group or dh returns
- * HP_ERR_UNSUPPORTED. */
+ * no float atomics.  patches_per_group <= 64, 0 <= num_joints <= 32, dh 16 / 24 / 32; another patches_per_group or dh (64
+ * included: that width takes hp_sformer_attention_backward) returns HP_ERR_UNSUPPORTED. */
 size_t hp_sformer_attention_backward_grouped_workspace_bytes(int B, int heads, int dh, int Ntok, int num_joints, int groups);
 int hp_sformer_attention_backward_grouped(const float* Q, const float* K, const float* K0, const float* V, const float* out,
                                           const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B,

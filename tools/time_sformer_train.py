@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """NlosPoseSformer training-step timing at the BASELINE config-5 geometry (dim 256, depth 8, 8 x 32 heads, patch 4, 16 frames
 of 128^2, fp32, seeded input): no-graph forward, graph-mode forward, backward, the library's per-kernel profile of one
-step, the attention backward's rate on the five-product count and the peak device memory.  One JSON line.
+step, the attention backward's rate on the five-product count and the peak device memory; the attention forward's kernel
+time in fp32 (from the step) and with fp16 patch attention (a no-graph forward of its own).  One JSON line.
 
-    python tools/time_sformer_train.py [--batch 8] [--steps 5] [--warmup 2]
+    python tools/time_sformer_train.py [--batch 8] [--steps 5] [--warmup 2] [--heads 8] [--dim-head 32]
+
+--heads / --dim-head change the head split only (dim stays 256): `--heads 4 --dim-head 64` is the same inner width, the same
+Q.K^T and P.V FLOPs and the same bytes as the default 8 x 32, with half the soft-max work.
 """
 from __future__ import annotations
 
@@ -39,9 +43,11 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--heads", type=int, default=8)
+    ap.add_argument("--dim-head", type=int, default=32)
     a = ap.parse_args()
-    kw = dict(dim=256, num_frames=16, num_joints=24, image_size=128, patch_size=4, channels=1, depth=8, heads=8, dim_head=32,
-              out_dim=512)
+    kw = dict(dim=256, num_frames=16, num_joints=24, image_size=128, patch_size=4, channels=1, depth=8, heads=a.heads,
+              dim_head=a.dim_head, out_dim=512)
     m = NlosPoseSformer(**kw)
     hpt.fill_module(m, "sformer.")
     m = m.cuda()
@@ -81,15 +87,31 @@ def main():
     torch.cuda.synchronize()
     prof = _lib.profile_read()
     _lib.profile_enable(False)
-    f, n, nj, heads, dh, depth = 16, 32 * 32, 24, 8, 32, 8
+    attn_fwd = lambda pr: sum(ms for k, (_, ms) in pr.items() if k.startswith("sformer_attention_"))
+    attn_fwd_ms = attn_fwd(prof)
+    # the same forward with the fp16 patch attention (no backward exists for it): a no-graph forward, profiled on its own
+    m.attention_precision = "fp16"
+    fwd_nograd()
+    _lib.profile_enable(True)
+    _lib.profile_reset()
+    fwd_nograd()
+    torch.cuda.synchronize()
+    prof16 = _lib.profile_read()
+    attn_fwd_fp16_ms = attn_fwd(prof16)
+    patch_fp16_ms = prof16.get("sformer_attention_patch", (0, 0.0))[1]
+    _lib.profile_enable(False)
+    m.attention_precision = "fp32"
+    f, n, nj, heads, dh, depth = 16, 32 * 32, 24, a.heads, a.dim_head, 8
     ntok = nj + f * n
     flops = depth * (5 * 2 * B * heads * f * n * (nj + n) * dh + 5 * 2 * B * heads * nj * ntok * dh)
     attn_ms = sum(ms for k, (_, ms) in prof.items() if k.startswith("sformer_attn_bwd"))
     rate = flops / (attn_ms * 1e-3) if attn_ms else 0.0
     print(json.dumps({
-        "config": "config5", "batch": B, "precision": "fp32",
+        "config": "config5", "batch": B, "precision": "fp32", "heads": a.heads, "dim_head": a.dim_head,
         "forward_nograd_ms": round(t_nograd, 2), "forward_graph_ms": round(t_graph, 2),
         "backward_ms": round(t_step - t_graph, 2), "step_ms": round(t_step, 2), "step_over_nograd_forward": round(t_step / t_nograd, 2),
+        "attention_forward_ms": round(attn_fwd_ms, 2), "attention_forward_fp16_ms": round(attn_fwd_fp16_ms, 2),
+        "attention_patch_fp16_ms": round(patch_fp16_ms, 2),
         "attention_backward_ms": round(attn_ms, 2), "attention_backward_tflops": round(rate / 1e12, 1),
         "attention_backward_fraction_of_fp32_mfma_peak": round(rate / FP32_MFMA_PEAK, 3),
         "peak_memory_gb": round(peak / 1e9, 2),

@@ -5,7 +5,11 @@ attention's backward (hp_sformer_attention_backward_grouped against the generic 
 inputs, same process, median of the timed calls); the device's maxGridSize; and whether the no-graph TimeSformer forward
 (time attention grid y = B * heads * hp * wp) launches at batch 8.  One JSON line.
 
-    python tools/time_xformer_train.py [--steps 5] [--warmup 2] [--ab-calls 20]
+    python tools/time_xformer_train.py [--steps 5] [--warmup 2] [--ab-calls 20] [--heads 8] [--dim-head 32]
+
+--heads / --dim-head set TimeSformer's head split (dim stays 256).  TokenPose-L keeps dim 192 and its 8 heads of 24 unless
+--dim-head is given: then it runs 192 // dim_head heads (3 heads of 64).  The grouped time-attention backward is not built
+for dim_head 64; the A/B is skipped there and the step takes the generic entry.
 
 TimeSformer: dim 256, depth 8, 8 heads x 32, 16 frames of 128^2, patch 4, 1 channel, batch 4.
 TokenPose-L: the models/token_config.py geometry (dim 192, 3 x depth 2, 8 heads x 24, 16 keypoints, 4 x 4 patches of a
@@ -134,7 +138,7 @@ def max_grid_size():
 
 
 def forward_batch8_launches(m):
-    """The no-graph forward at batch 8 (time attention grid y = 8 * 8 * 1024 = 65536) against two batch-4 halves."""
+    """The no-graph forward at batch 8 (time attention grid y = 8 * heads * 1024; 65536 at 8 heads) against two batch-4 halves."""
     video = torch.rand(8, 16, 1, 128, 128, generator=torch.Generator().manual_seed(9)).cuda()
     try:
         with torch.no_grad():
@@ -151,12 +155,22 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--ab-calls", type=int, default=20)
+    ap.add_argument("--heads", type=int, default=TS_KW["heads"])
+    ap.add_argument("--dim-head", type=int, default=None)
     a = ap.parse_args()
+    TS_KW.update(heads=a.heads, dim_head=a.dim_head or TS_KW["dim_head"])
+    if a.dim_head:
+        assert TP_KW["dim"] % a.dim_head == 0, "TokenPose-L: dim 192 must be a multiple of --dim-head"
+        TP_KW.update(heads=TP_KW["dim"] // a.dim_head)
     out = {"precision": "fp32", "time_attention_backward": xa.TIME_ATTENTION_BACKWARD, "max_grid_size": max_grid_size()}
     ts = TimeSformer(**TS_KW)
     hpt.fill_module(ts, "timesformer.")
     ts = ts.cuda()
-    out["timesformer_time_attention_backward_ab"] = time_attention_ab(ts, 4, a.ab_calls)
+    out["geometry"] = {"timesformer": [TS_KW["heads"], TS_KW["dim_head"]], "tokenpose_l": [TP_KW["heads"], TP_KW["dim"] // TP_KW["heads"]]}
+    if TS_KW["dim_head"] in xa.GROUPED_DIM_HEADS:
+        out["timesformer_time_attention_backward_ab"] = time_attention_ab(ts, 4, a.ab_calls)
+    else:
+        out["timesformer_time_attention_backward_ab"] = {"skipped": "the grouped entry is not built for this dim_head"}
     video = torch.rand(4, 16, 1, 128, 128, generator=torch.Generator().manual_seed(5)).cuda()
     R = torch.randn(4, 72, generator=torch.Generator().manual_seed(6)).cuda()
     out["timesformer"] = {"batch": 4, "depth": 8, **head_timing(ts, video, R, a.steps, a.warmup)}
