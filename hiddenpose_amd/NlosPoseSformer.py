@@ -65,6 +65,7 @@ class _FeedForward(nn.Module):
 
 
 _LINEAR_PRECISION = {"fp32": 0, "bf16": 1, "bf16x3": 2, "bf16x6": 3}  # HP_PRECISION_*
+_ATTENTION_PRECISION = {"fp32": 0, "bf16": 1, "fp16": 4}
 
 
 def _linear(x2d, weight, bias, precision=0, residual=None):
@@ -83,6 +84,10 @@ class NlosPoseSformer(nn.Module):
     linear_precision = "fp32"
     # patch-token attention: "fp32" (exact-fp32 MFMA, default), "bf16" or "fp16" (16-bit matrix cores, fp32 soft-max; dim_head 32 or 64)
     attention_precision = "fp32"
+    # attention backward: "fp32" (exact, default; needs attention_precision "fp32") or "bf16" / "fp16": the patch queries'
+    # part of the backward on the 16-bit matrix cores (dim_head 32 or 64; the joint queries stay exact fp32), after a forward
+    # at either attention_precision
+    attention_backward_precision = "fp32"
 
     def __init__(self, *, dim, num_frames, num_joints=24, image_size=224, patch_size=16, channels=2, depth=12, heads=8,
                  dim_head=64, attn_dropout=0.0, ff_dropout=0.0, rotary_emb=True, out_dim=64 * 2 * 3, batch_size=2):
@@ -106,9 +111,9 @@ class NlosPoseSformer(nn.Module):
     def forward(self, video, mask=None):
         """An autograd graph is built when grad mode is on, the module is in training mode or `video` requires grad, and
         something (a parameter or `video`) requires grad.  Its forward runs the same kernels in the same order as the
-        no-graph path (the output is bit-identical) and keeps what backward needs; backward needs
-        attention_precision "fp32" and no dropout.  Otherwise (eval mode on a plain input, or no_grad) the no-graph path
-        runs, launch for launch as an inference-only module would."""
+        no-graph path (the output is bit-identical) and keeps what backward needs; backward needs no dropout and
+        either attention_precision "fp32" or a 16-bit attention_backward_precision.  Otherwise (eval mode on a plain input, or
+        no_grad) the no-graph path runs, launch for launch as an inference-only module would."""
         assert mask is None, "frame masks are ignored by the reference's attention (:177-179) and not supported"
         if not video.is_cuda:
             raise _lib.HiddenPoseHipError("NlosPoseSformer.forward needs a tensor on a HIP device; there is no CPU path")
@@ -118,11 +123,15 @@ class NlosPoseSformer(nn.Module):
             if self.attn_dropout > 0 or self.ff_dropout > 0:
                 raise _lib.HiddenPoseHipError("NlosPoseSformer training: dropout is not built (attn_dropout / ff_dropout must be 0)")
             aprec = {"fp32": 0, "bf16": 1, "fp16": 4}[self.attention_precision]
-            if aprec and self.dim_head not in (32, 64):
+            if self.attention_backward_precision not in _ATTENTION_PRECISION:
+                raise _lib.HiddenPoseHipError(f"attention_backward_precision {self.attention_backward_precision!r}: one of "
+                                              "\"fp32\", \"bf16\", \"fp16\"")
+            bprec = _ATTENTION_PRECISION[self.attention_backward_precision]
+            if (aprec or bprec) and self.dim_head not in (32, 64):
                 raise _lib.HiddenPoseHipError("bf16 / fp16 attention is built for dim_head 32 and 64 only")
             with torch.cuda.device(video.device):
                 return _xa.SformerFunction.apply(video.contiguous().float(), self, _LINEAR_PRECISION[self.linear_precision], aprec,
-                                                 *params)
+                                                 bprec, *params)
         with torch.no_grad():
             return self._forward_nograd(video)
 

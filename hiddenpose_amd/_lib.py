@@ -133,6 +133,10 @@ SIGNATURES = {
     "hp_sformer_attention_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "hp_sformer_attention_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i,
                                            _vp, _sz, _vp]),
+    "hp_sformer_attention_lse_p": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "hp_sformer_attention_backward_p_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "hp_sformer_attention_backward_p": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i,
+                                             _vp, _sz, _vp]),
     "hp_sformer_qkv_prepare_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, C.c_float, _fp, _fp, _i, _vp]),
     "hp_layernorm_backward_workspace_bytes": (_sz, [C.c_long, _i]),
     "hp_layernorm_backward": (_i, [_fp, _fp, _fp, _fp, _fp, C.c_long, _i, _fp, C.c_float, _i, C.c_long, _vp, _sz, _vp]),

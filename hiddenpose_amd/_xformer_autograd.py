@@ -73,14 +73,23 @@ def geglu_backward(u, dg):
     return du
 
 
-def attention_backward(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, frames):
+def attention_backward(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, frames, precision=0):
+    """(dQ, dK, dK0, dV).  precision 0: the exact-fp32 backward; 1 (bf16) / 4 (fp16): the patch queries' part on the 16-bit
+    matrix cores (hp_sformer_attention_backward_p; dim_head 32 or 64), the joint queries' part exact fp32."""
     L = _lib.lib()
     dq, dk, dk0, dv = (torch.empty_like(q) for _ in range(4))
-    nb = L.hp_sformer_attention_backward_workspace_bytes(b, heads, dh, ntok, nj, frames)
+    if precision == 0:
+        nb = L.hp_sformer_attention_backward_workspace_bytes(b, heads, dh, ntok, nj, frames)
+        ws = _ws(nb, q.device)
+        _lib.check(L.hp_sformer_attention_backward(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
+                                                   lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), b, heads, dh, ntok,
+                                                   nj, n, frames, ws.data_ptr(), nb, _st(q)), "hp_sformer_attention_backward")
+        return dq, dk, dk0, dv
+    nb = L.hp_sformer_attention_backward_p_workspace_bytes(b, heads, dh, ntok, nj, frames, precision)
     ws = _ws(nb, q.device)
-    _lib.check(L.hp_sformer_attention_backward(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                               lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), b, heads, dh, ntok,
-                                               nj, n, frames, ws.data_ptr(), nb, _st(q)), "hp_sformer_attention_backward")
+    _lib.check(L.hp_sformer_attention_backward_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
+                                                 lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), b, heads, dh, ntok,
+                                                 nj, n, frames, precision, ws.data_ptr(), nb, _st(q)), "hp_sformer_attention_backward_p")
     return dq, dk, dk0, dv
 
 
@@ -105,10 +114,11 @@ def trainable_params(m):
 
 
 class SformerFunction(torch.autograd.Function):
-    """video (b, f, c, H, W), *trainable_params(m) -> (b, num_joints, 4, out_dim / 4)."""
+    """video (b, f, c, H, W), module, three precisions, *trainable_params(m) -> (b, num_joints, 4, out_dim / 4)."""
 
     @staticmethod
-    def forward(ctx, video, m, prec, aprec, *params):
+    def forward(ctx, video, m, prec, aprec, bprec, *params):
+        """prec, aprec, bprec: HP_PRECISION_* of the Linear layers, the patch attention's forward and the attention backward."""
         L = _lib.lib()
         b, f, c, H, W = video.shape
         ps, nj, heads, dh = m.patch_size, m.num_joints, m.heads, m.dim_head
@@ -149,6 +159,10 @@ class SformerFunction(torch.autograd.Function):
                 lse = torch.empty(b, heads, ntok, dtype=torch.float32, device=dev)
                 _lib.check(L.hp_sformer_attention_lse(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(),
                                                       b, heads, dh, ntok, nj, n, f, aws.data_ptr(), st), "hp_sformer_attention_lse")
+            elif bprec != 0:   # a 16-bit backward recomputes P from the 16-bit forward's own lse
+                lse = torch.empty(b, heads, ntok, dtype=torch.float32, device=dev)
+                _lib.check(L.hp_sformer_attention_lse_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(),
+                                                        b, heads, dh, ntok, nj, n, f, aprec, aws.data_ptr(), st), "hp_sformer_attention_lse_p")
             else:
                 _lib.check(L.hp_sformer_attention(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh,
                                                   ntok, nj, n, f, aprec, aws.data_ptr(), st), "hp_sformer_attention")
@@ -172,7 +186,7 @@ class SformerFunction(torch.autograd.Function):
         _lib.check(L.hp_layernorm_forward(x.data_ptr(), jt.data_ptr(), b * nj, dim, params[-4].data_ptr(), params[-3].data_ptr(),
                                           m.to_out[0].eps, nj, ntok, st), "hp_layernorm_forward")
         out = linear(jt, params[-2], params[-1])
-        ctx.geom = (b, f, c, H, W, ps, nj, heads, dh, n, ntok, dim, rot_dim, prec, aprec)
+        ctx.geom = (b, f, c, H, W, ps, nj, heads, dh, n, ntok, dim, rot_dim, prec, aprec, bprec)
         ctx.consts = [(layer[1].fn.scale, layer[1].norm.eps, layer[2].norm.eps) for layer in m.layers] + [m.to_out[0].eps]
         ctx.depth = len(m.layers)
         ctx.nsaved = len(saved)
@@ -181,10 +195,11 @@ class SformerFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        b, f, c, H, W, ps, nj, heads, dh, n, ntok, dim, rot_dim, prec, aprec = ctx.geom
-        if aprec != 0:
+        b, f, c, H, W, ps, nj, heads, dh, n, ntok, dim, rot_dim, prec, aprec, bprec = ctx.geom
+        if aprec != 0 and bprec == 0:
             raise _lib.HiddenPoseHipError("NlosPoseSformer backward: training needs attention_precision = \"fp32\" (the bf16 / fp16 "
-                                          "patch attention has no backward)")
+                                          "patch attention has no fp32 backward) or attention_backward_precision = \"bf16\" / "
+                                          "\"fp16\"")
         L = _lib.lib()
         allt = ctx.saved_tensors
         saved, (tokens, xl, jt, sin_t, cos_t), params = allt[:ctx.nsaved], allt[ctx.nsaved:ctx.nsaved + 5], allt[ctx.nsaved + 5:]
@@ -214,7 +229,7 @@ class SformerFunction(torch.autograd.Function):
             del dh2
             # attention: x1 = x + Wo att + bo
             datt, grads[base + 3], grads[base + 4] = linear_backward(att.view(rows, inner), d2, wo, prec)
-            dq, dk, dk0, dv = attention_backward(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, f)
+            dq, dk, dk0, dv = attention_backward(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, f, bprec)
             del datt
             dqkv = torch.empty(rows, 3 * inner, dtype=torch.float32, device=dev)
             _lib.check(L.hp_sformer_qkv_prepare_backward(dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), dqkv.data_ptr(), b,
@@ -237,7 +252,7 @@ class SformerFunction(torch.autograd.Function):
         if need_video:
             dvideo = torch.empty(b, f, c, H, W, dtype=torch.float32, device=dev)
             _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dvideo.data_ptr(), b, f, c, H, W, ps, st), "hp_sformer_unpatchify")
-        return (dvideo, None, None, None, *grads)
+        return (dvideo, None, None, None, None, *grads)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -26,6 +26,13 @@ struct ProfScope {
 };
 #define HP_PROF(name, stream) ::hp::ProfScope _hp_prof_scope(name, stream)
 
+// Exact-fp32 launches of sformer_backward.hip that the 16-bit attention backward (sformer_backward16.hip) reuses (dh 32 / 64).
+constexpr int ATTN_BWD_DQ_SPLITS = 32;   // key splits of the joint queries' dQ partials (32 queries x dh floats each)
+void launch_attn_bwd_joint_keys(const float* ws_dk, const float* ws_dv, float* dK, float* dV, int BH, int Ntok, int dh, int nj, int frames,
+                                hipStream_t st);
+void launch_attn_bwd_dq_joint(const float* Q, const float* K0, const float* V, const float* dout, const float* lse, const float* delta,
+                              float* part, float* dQ, int BH, int heads, int dh, int Ntok, int nj, hipStream_t st);
+
 // ---- activation tensors stored as fp32 or bf16 (BASELINE configs[2]: bf16 with fp32 accumulators / statistics).  The
 // element type of a tensor is a RUNTIME flag of the call (`half` != 0: bf16), so one kernel serves both layouts: the
 // branch is uniform over the launch and the conversion is a shift (load) or one v_cvt_pk_bf16_f32 per pair (store).

@@ -25,7 +25,7 @@ namespace hp {
 constexpr int SB = 256;   // threads per block
 constexpr int QT = 64;    // query rows per LDS tile of the dkv sweep
 constexpr int KT = 64;    // key rows per LDS tile of the dq sweep
-constexpr int DQ_SPLITS = 32;
+constexpr int DQ_SPLITS = ATTN_BWD_DQ_SPLITS;
 
 static unsigned bgrid(long n) { return (unsigned)std::max<long>(1, std::min<long>((n + SB - 1) / SB, 256 * 8)); }
 
@@ -929,6 +929,26 @@ extern "C" int hp_sformer_attention_backward(const float* Q, const float* K, con
   HP_CHECK_HIP(hipGetLastError());
   return HP_OK;
 }
+
+// The exact-fp32 pieces the 16-bit backward (sformer_backward16.hip) shares with this file, launched on `st`:
+// the joint keys' per-frame dK / dV partials summed in frame order, and dQ of the joint queries (splits + ordered merge).
+namespace hp {
+void launch_attn_bwd_joint_keys(const float* ws_dk, const float* ws_dv, float* dK, float* dV, int BH, int Ntok, int dh, int nj, int frames,
+                                hipStream_t st) {
+  const long total = (long)BH * nj * dh;
+  hipLaunchKernelGGL(k_attn_bwd_joint_keys, dim3((unsigned)((total + SB - 1) / SB)), dim3(SB), 0, st, ws_dk, ws_dv, dK, dV, BH, Ntok, dh, nj,
+                     frames);
+}
+void launch_attn_bwd_dq_joint(const float* Q, const float* K0, const float* V, const float* dout, const float* lse, const float* delta,
+                              float* part, float* dQ, int BH, int heads, int dh, int Ntok, int nj, hipStream_t st) {
+  const int nsplit = std::max(1, std::min(DQ_SPLITS, (Ntok + 255) / 256));
+  const dim3 gj(nsplit, BH);
+  if (dh == 64) hipLaunchKernelGGL(k_attn_bwd_dq_joint64, gj, dim3(SB), 0, st, Q, K0, V, dout, lse, delta, part, heads, Ntok, nj);
+  else hipLaunchKernelGGL((k_attn_bwd_dq_joint<32>), gj, dim3(SB), 0, st, Q, K0, V, dout, lse, delta, part, heads, Ntok, nj);
+  const long total = (long)BH * nj * dh;
+  hipLaunchKernelGGL(k_attn_bwd_dq_joint_merge, dim3((unsigned)((total + SB - 1) / SB)), dim3(SB), 0, st, part, dQ, BH, Ntok, dh, nj, nsplit);
+}
+}  // namespace hp
 
 // groups per workgroup of k_attn_bwd_grouped: as many whole groups as G (nj + n) <= SB threads allow, while the LDS images
 // stay within 64 KiB

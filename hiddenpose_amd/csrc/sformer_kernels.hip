@@ -305,16 +305,20 @@ __global__ __launch_bounds__(ST) void k_attention(const float* __restrict__ Q, c
 // and the V tile is staged transposed with its keys in that slot order, so both P and V^T are one 16-byte read.
 // H = __bf16 (v_mfma_f32_32x32x16_bf16) or _Float16 (v_mfma_f32_32x32x16_f16: the "MFMA fp16 attention" of BASELINE
 // configs[4] to the letter; 11 significand bits instead of 8 on Q, K, V and the probabilities, same rate, same dataflow).
+constexpr float LN2 = 0.6931471805599453f;
 template <typename H>
 __device__ __forceinline__ f32x16 mfma_h16(const __attribute__((ext_vector_type(8))) H a, const __attribute__((ext_vector_type(8))) H b,
                                            f32x16 c) {
   if constexpr (std::is_same<H, _Float16>::value) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
   else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
-template <typename H>
+// LSE: also store the patch queries' log-sum-exp, back in the natural-log domain: ln 2 (m + log2 l); `out` is the same
+// arithmetic in both instantiations.
+template <typename H, bool LSE = false>
 __global__ __launch_bounds__(ST) void k_attention_patch_h16(const float* __restrict__ Q, const float* __restrict__ K,
                                                              const float* __restrict__ V, float* __restrict__ out, int heads,
-                                                             int Ntok, int nj, int n, int frames) {
+                                                             int Ntok, int nj, int n, int frames,
+                                                             float* __restrict__ lse = nullptr) {
   constexpr int DH = 32, LDB = DH + 8;  // 80-byte rows: the 16-byte fragment reads of 32 rows spread over all banks
   using bf16x8s = __attribute__((ext_vector_type(8))) H;
   __shared__ __attribute__((aligned(16))) H Kh[32 * LDB];   // [key][d]
@@ -431,6 +435,7 @@ __global__ __launch_bounds__(ST) void k_attention_patch_h16(const float* __restr
     const int d = (r & 3) + 8 * (r >> 2) + 4 * half;
     o[col * (DH + 1) + d] = oacc[r] * inv;
   }
+  if (LSE && qvalid && half == 0) lse[(long)bh * Ntok + qtok] = LN2 * (m + log2f(l));
   __syncthreads();
   for (int i = lane; i < 32 * DH; i += 64) {
     const int qr = i / DH, d = i - qr * DH;
@@ -659,10 +664,11 @@ __global__ __launch_bounds__(ST) void k_attention64(const float* __restrict__ Q,
 // the next tile's rows requested before the current tile's arithmetic).  Per 32-key tile: 4 MFMAs for S^T (k = d in four
 // steps of 16) and 2 x 2 for the two O^T accumulators, against the same 512 exp2 per wave as at 32: twice the matrix
 // work per unit of soft-max work.  K rows are 72 halves (144 bytes), V^T is [64 d][32 key slots + 8].
-template <typename H>
+template <typename H, bool LSE = false>
 __global__ __launch_bounds__(ST) void k_attention_patch_h16_64(const float* __restrict__ Q, const float* __restrict__ K,
                                                                 const float* __restrict__ V, float* __restrict__ out, int heads,
-                                                                int Ntok, int nj, int n, int frames) {
+                                                                int Ntok, int nj, int n, int frames,
+                                                                float* __restrict__ lse = nullptr) {
   constexpr int DH = 64, LDB = DH + 8, LDV = 32 + 8;
   using bf16x8s = __attribute__((ext_vector_type(8))) H;
   __shared__ __attribute__((aligned(16))) H Kh[32 * LDB];   // [key][d]
@@ -786,6 +792,7 @@ __global__ __launch_bounds__(ST) void k_attention_patch_h16_64(const float* __re
     o[col * (DH + 1) + d] = oacc0[r] * inv;
     o[col * (DH + 1) + 32 + d] = oacc1[r] * inv;
   }
+  if (LSE && qi < n && half == 0) lse[(long)bh * Ntok + nj + f * n + qi] = LN2 * (m + log2f(l));
   __syncthreads();
   for (int i = lane; i < 32 * DH; i += 64) {
     const int qr = i / DH, d = i - qr * DH;
@@ -940,6 +947,48 @@ extern "C" int hp_sformer_attention_lse(const float* Q, const float* K, const fl
     else if (dh == 32) hipLaunchKernelGGL((k_attention<32>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
     else if (dh == 24) hipLaunchKernelGGL((k_attention<24>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
     else hipLaunchKernelGGL((k_attention<16>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
+    const int total = B * heads * num_joints * dh;
+    hipLaunchKernelGGL(k_attention_joint_merge, dim3((total + 255) / 256), dim3(256), 0, st, part, out, B * heads, heads, dh, Ntok,
+                       num_joints, nsplit, lse);
+  }
+  HP_CHECK_HIP(hipGetLastError());
+  return HP_OK;
+}
+
+// hp_sformer_attention at any precision with the log-sum-exp of every query.  FP32 is hp_sformer_attention_lse; BF16 / FP16
+// run hp_sformer_attention's launches with the LSE instantiation of the 16-bit patch kernel (`out` keeps its bits) and the
+// joint merge's lse store.
+extern "C" int hp_sformer_attention_lse_p(const float* Q, const float* K, const float* K0, const float* V, float* out, float* lse, int B,
+                                          int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
+                                          int precision, void* workspace, void* stream) {
+  if (precision == HP_PRECISION_FP32)
+    return hp_sformer_attention_lse(Q, K, K0, V, out, lse, B, heads, dh, Ntok, num_joints, patches_per_frame, frames, workspace, stream);
+  HP_REQUIRE(Q && K && K0 && V && out && lse && workspace, "hp_sformer_attention_lse_p: null argument");
+  HP_REQUIRE(num_joints <= 32 && Ntok == num_joints + frames * patches_per_frame, "hp_sformer_attention_lse_p: bad token layout");
+  HP_REQUIRE(precision == HP_PRECISION_BF16 || precision == HP_PRECISION_FP16, "hp_sformer_attention_lse_p: precision %d not built",
+             precision);
+  if (dh != 32 && dh != 64) {
+    set_error("hp_sformer_attention_lse_p: the 16-bit patch attention is built for dim_head 32 and 64, not %d", dh);
+    return HP_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int ntiles = (Ntok + 31) / 32;
+  const int nsplit = std::max(1, std::min(JOINT_SPLITS, ntiles / 4));
+  float* part = (float*)workspace;
+  const dim3 gp((patches_per_frame + 127) / 128, B * heads * frames), gj(nsplit, B * heads);
+  {
+    HP_PROF("sformer_attention_patch", st);
+#define HP_P16(KERN, T) hipLaunchKernelGGL((KERN<T, true>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, num_joints, patches_per_frame, frames, lse)
+    if (dh == 64 && precision == HP_PRECISION_BF16) HP_P16(k_attention_patch_h16_64, __bf16);
+    else if (dh == 64) HP_P16(k_attention_patch_h16_64, _Float16);
+    else if (precision == HP_PRECISION_BF16) HP_P16(k_attention_patch_h16, __bf16);
+    else HP_P16(k_attention_patch_h16, _Float16);
+#undef HP_P16
+  }
+  if (num_joints > 0) {
+    HP_PROF("sformer_attention_joint", st);
+    if (dh == 64) hipLaunchKernelGGL((k_attention64<false>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, (float*)nullptr);
+    else hipLaunchKernelGGL((k_attention<32>), gj, dim3(ST), 0, st, Q, K0, V, out, heads, Ntok, num_joints, patches_per_frame, frames, 1, part, nullptr);
     const int total = B * heads * num_joints * dh;
     hipLaunchKernelGGL(k_attention_joint_merge, dim3((total + 255) / 256), dim3(256), 0, st, part, out, B * heads, heads, dh, Ntok,
                        num_joints, nsplit, lse);

@@ -491,6 +491,30 @@ int hp_sformer_attention_backward(const float* Q, const float* K, const float* K
                                   const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B,
                                   int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
                                   void* workspace, size_t workspace_bytes, void* stream);
+/* Mixed-precision training of the attention: the two entries above with a `precision` argument.
+ * hp_sformer_attention_lse_p: HP_PRECISION_FP32 is hp_sformer_attention_lse.  HP_PRECISION_BF16 / HP_PRECISION_FP16 (dh 32 or
+ * 64; another dh returns HP_ERR_UNSUPPORTED): `out` is bit-identical to hp_sformer_attention(..., precision, ...) and lse is
+ * the natural-log sum of exp of each query's scores as the kernel computed them (the 16-bit patch kernels keep their scores
+ * in the log2 domain: lse = ln 2 (m + log2 l)); the joint queries' rows come from the fp32 joint kernel, as in
+ * hp_sformer_attention_lse.  Same workspace as hp_sformer_attention.
+ * hp_sformer_attention_backward_p: HP_PRECISION_FP32 forwards to hp_sformer_attention_backward (bitwise).  BF16 / FP16:
+ * everything that involves a PATCH query (its dQ, its contribution to dK and dV of its frame's keys and of the joint keys)
+ * runs on v_mfma_f32_32x32x16_{bf16,f16}: Q, K, V, dO, P and dS are rounded to the 16-bit type as operands, the scores, the
+ * exponential, dS and every accumulation stay fp32, P is recomputed from lse.  Everything that involves a JOINT query (its dQ,
+ * dK0, its share of dV) stays exact fp32.  `out` and lse may come from either forward precision.  dh 32 and 64 (another dh
+ * returns HP_ERR_UNSUPPORTED), 0 <= num_joints <= 32, any patches_per_frame >= 1 and frame count with B * heads * frames
+ * < 65536; another precision value is refused.  The rows of Q, K, K0, V, out, dout are read 16 bytes at a time: their base
+ * addresses must be 16-byte aligned.  The contract of this section holds: no float atomics, every sum in a fixed order (the
+ * joint keys' per-frame partials in frame order), two calls give identical bits. */
+int hp_sformer_attention_lse_p(const float* Q, const float* K, const float* K0, const float* V, float* out, float* lse, int B,
+                               int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames, int precision,
+                               void* workspace, void* stream);
+size_t hp_sformer_attention_backward_p_workspace_bytes(int B, int heads, int dh, int Ntok, int num_joints, int frames,
+                                                       int precision);
+int hp_sformer_attention_backward_p(const float* Q, const float* K, const float* K0, const float* V, const float* out,
+                                    const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B,
+                                    int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames, int precision,
+                                    void* workspace, size_t workspace_bytes, void* stream);
 /* hp_sformer_attention_backward for short groups (TimeSformer's time attention on the transposed token grid: groups =
  * hp*wp patch positions of patches_per_group = frames tokens).  Same arguments, layout Ntok = num_joints + groups *
  * patches_per_group, outputs and reduction order (joint-key partials summed in group order, joint-query dQ split and merged

@@ -5,6 +5,13 @@ step, the attention backward's rate on the five-product count and the peak devic
 time in fp32 (from the step) and with fp16 patch attention (a no-graph forward of its own).  One JSON line.
 
     python tools/time_sformer_train.py [--batch 8] [--steps 5] [--warmup 2] [--heads 8] [--dim-head 32]
+                                       [--attention fp32|bf16|fp16] [--attention-backward fp32|bf16|fp16] [--linear fp32|bf16]
+
+--attention / --attention-backward are NlosPoseSformer.attention_precision / attention_backward_precision (a 16-bit forward
+needs a 16-bit backward to train).  The attention backward's time is reported on the same five-product FLOP count at every
+precision, as a fraction of the fp32 MFMA peak, of the 2.5 PF/s bf16 MFMA peak, and as exponentials per second (two per score:
+the key pass and the query pass each recompute P), since at dim_head 32 the 16-bit attention is bound by v_exp_f32 and the
+MFMA fraction alone is the wrong yardstick.
 
 --heads / --dim-head change the head split only (dim stays 256): `--heads 4 --dim-head 64` is the same inner width, the same
 Q.K^T and P.V FLOPs and the same bytes as the default 8 x 32, with half the soft-max work.
@@ -27,6 +34,7 @@ from hiddenpose_amd import testing as hpt  # noqa: E402
 from hiddenpose_amd.NlosPoseSformer import NlosPoseSformer  # noqa: E402
 
 FP32_MFMA_PEAK = 157.3e12
+BF16_MFMA_PEAK = 2.5e15
 
 
 def timed(fn, steps):
@@ -45,12 +53,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--dim-head", type=int, default=32)
+    ap.add_argument("--attention", choices=("fp32", "bf16", "fp16"), default="fp32")
+    ap.add_argument("--attention-backward", choices=("fp32", "bf16", "fp16"), default="fp32")
+    ap.add_argument("--linear", choices=("fp32", "bf16"), default="fp32")
     a = ap.parse_args()
+    if a.attention != "fp32" and a.attention_backward == "fp32":
+        ap.error("a 16-bit --attention trains only with a 16-bit --attention-backward")
     kw = dict(dim=256, num_frames=16, num_joints=24, image_size=128, patch_size=4, channels=1, depth=8, heads=a.heads,
               dim_head=a.dim_head, out_dim=512)
     m = NlosPoseSformer(**kw)
     hpt.fill_module(m, "sformer.")
     m = m.cuda()
+    m.attention_precision, m.attention_backward_precision, m.linear_precision = a.attention, a.attention_backward, a.linear
     B = a.batch
     video = torch.rand(B, 16, 1, 128, 128, generator=torch.Generator().manual_seed(5)).cuda()
     R = torch.randn(B, 24, 4, 128, generator=torch.Generator().manual_seed(6)).cuda()
@@ -89,7 +103,7 @@ def main():
     _lib.profile_enable(False)
     attn_fwd = lambda pr: sum(ms for k, (_, ms) in pr.items() if k.startswith("sformer_attention_"))
     attn_fwd_ms = attn_fwd(prof)
-    # the same forward with the fp16 patch attention (no backward exists for it): a no-graph forward, profiled on its own
+    # the same forward with the fp16 patch attention: a no-graph forward, profiled on its own
     m.attention_precision = "fp16"
     fwd_nograd()
     _lib.profile_enable(True)
@@ -100,20 +114,24 @@ def main():
     attn_fwd_fp16_ms = attn_fwd(prof16)
     patch_fp16_ms = prof16.get("sformer_attention_patch", (0, 0.0))[1]
     _lib.profile_enable(False)
-    m.attention_precision = "fp32"
+    m.attention_precision = a.attention
     f, n, nj, heads, dh, depth = 16, 32 * 32, 24, a.heads, a.dim_head, 8
     ntok = nj + f * n
     flops = depth * (5 * 2 * B * heads * f * n * (nj + n) * dh + 5 * 2 * B * heads * nj * ntok * dh)
     attn_ms = sum(ms for k, (_, ms) in prof.items() if k.startswith("sformer_attn_bwd"))
     rate = flops / (attn_ms * 1e-3) if attn_ms else 0.0
+    exps = depth * 2 * (B * heads * f * n * (nj + n) + B * heads * nj * ntok)
     print(json.dumps({
-        "config": "config5", "batch": B, "precision": "fp32", "heads": a.heads, "dim_head": a.dim_head,
+        "config": "config5", "batch": B, "precision": a.linear, "attention": a.attention, "attention_backward": a.attention_backward,
+        "heads": a.heads, "dim_head": a.dim_head,
         "forward_nograd_ms": round(t_nograd, 2), "forward_graph_ms": round(t_graph, 2),
         "backward_ms": round(t_step - t_graph, 2), "step_ms": round(t_step, 2), "step_over_nograd_forward": round(t_step / t_nograd, 2),
         "attention_forward_ms": round(attn_fwd_ms, 2), "attention_forward_fp16_ms": round(attn_fwd_fp16_ms, 2),
         "attention_patch_fp16_ms": round(patch_fp16_ms, 2),
         "attention_backward_ms": round(attn_ms, 2), "attention_backward_tflops": round(rate / 1e12, 1),
         "attention_backward_fraction_of_fp32_mfma_peak": round(rate / FP32_MFMA_PEAK, 3),
+        "attention_backward_fraction_of_bf16_mfma_peak": round(rate / BF16_MFMA_PEAK, 4),
+        "attention_backward_gexp_per_s": round(exps / (attn_ms * 1e-3) / 1e9, 1) if attn_ms else 0.0,
         "peak_memory_gb": round(peak / 1e9, 2),
         "kernels_ms": {k: [cnt, round(ms, 3)] for k, (cnt, ms) in sorted(prof.items(), key=lambda kv: -kv[1][1])},
     }))
