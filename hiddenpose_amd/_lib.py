@@ -145,6 +145,14 @@ SIGNATURES = {
     "hp_sformer_attention_backward_grouped_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "hp_sformer_attention_backward_grouped": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i,
                                                    _i, _vp, _sz, _vp]),
+    "hp_sformer_attention_masked": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "hp_sformer_attention_lse_masked": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "hp_sformer_attention_backward_masked_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "hp_sformer_attention_backward_masked": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i,
+                                                  _vp, _i, _vp, _sz, _vp]),
+    "hp_sformer_attention_backward_grouped_masked_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "hp_sformer_attention_backward_grouped_masked": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i,
+                                                          _i, _i, _vp, _i, _vp, _sz, _vp]),
     "hp_linear_backward_data_workspace_bytes": (_sz, [_i, _i]),
     "hp_linear_backward_data": (_i, [_fp, _fp, _fp, _fp, C.c_long, _i, _i, _i, _vp, _sz, _vp]),
     "hp_linear_backward_weight_workspace_bytes": (_sz, [C.c_long, _i, _i]),

@@ -34,10 +34,14 @@ def layernorm(x2d, norm, rows=None, rows_per_batch=0, batch_stride_rows=0):
     return y
 
 
-def attention(h2d, to_qkv, b, ntok, heads, dh, nj, n, frames, scale, sin_t=None, cos_t=None, precision=0):
+def attention(h2d, to_qkv, b, ntok, heads, dh, nj, n, frames, scale, sin_t=None, cos_t=None, precision=0, key_mask=None,
+              mask_patch_queries=False):
     """Multi-head attention over tokens [nj class / joint tokens | frames groups of n tokens]: the class tokens attend
     to every token (keys without rotary embedding), a group's tokens to [class tokens | their group] with the rotary
-    tables (n, rot_dim) applied to q and k.  h2d: (b * ntok, dim) normalised input -> (b, ntok, heads * dh)."""
+    tables (n, rot_dim) applied to q and k.  h2d: (b * ntok, dim) normalised input -> (b, ntok, heads * dh).
+    key_mask: None (today's call, launch for launch) or a (b, ntok) uint8 tensor in this call's token order, nonzero =
+    attendable (hp_sformer_attention_masked): the class queries leave the masked tokens out, the group queries too when
+    mask_patch_queries."""
     L = _lib.lib()
     dev = h2d.device
     inner = heads * dh
@@ -49,9 +53,23 @@ def attention(h2d, to_qkv, b, ntok, heads, dh, nj, n, frames, scale, sin_t=None,
                                         n, scale, _lib.ptr(sin_t), _lib.ptr(cos_t), rot_dim, _st(h2d)), "hp_sformer_qkv_prepare")
     att = torch.empty(b, ntok, inner, dtype=torch.float32, device=dev)
     ws = torch.empty(max(1, int(L.hp_sformer_attention_workspace_bytes(b, heads, dh)) // 4), dtype=torch.float32, device=dev)
-    _lib.check(L.hp_sformer_attention(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh, ntok, nj, n,
-                                      frames, 0, ws.data_ptr(), _st(h2d)), "hp_sformer_attention")
+    if key_mask is None:
+        _lib.check(L.hp_sformer_attention(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh, ntok, nj, n,
+                                          frames, 0, ws.data_ptr(), _st(h2d)), "hp_sformer_attention")
+    else:
+        check_key_mask(key_mask, b, ntok, dev)
+        _lib.check(L.hp_sformer_attention_masked(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh, ntok,
+                                                 nj, n, frames, key_mask.data_ptr(), int(bool(mask_patch_queries)), ws.data_ptr(),
+                                                 _st(h2d)), "hp_sformer_attention_masked")
     return att
+
+
+def check_key_mask(key_mask, b, ntok, dev):
+    """The masked attention entries read b * ntok bytes at key_mask's address: anything else is refused here."""
+    if (key_mask.dtype != torch.uint8 or tuple(key_mask.shape) != (b, ntok) or key_mask.device != dev
+            or not key_mask.is_contiguous()):
+        raise ValueError(f"key_mask must be a contiguous uint8 tensor of shape ({b}, {ntok}) on {dev}; got "
+                         f"{key_mask.dtype} {tuple(key_mask.shape)} on {key_mask.device}")
 
 
 def geglu_ff(x2d_resid, h2d, lin_in, lin_out, precision=0):

@@ -266,6 +266,21 @@ def gelu_backward(u, dy):
     return dy
 
 
+def attention_backward_masked(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, groups, key_mask, mask_patch_queries,
+                              grouped=False):
+    """(dQ, dK, dK0, dV) of the fp32 attention with a key mask (hp_sformer_attention_backward_masked, or its grouped form
+    for n <= 64 tokens per group at dim_head 16 / 24 / 32; the two are bit-equal)."""
+    L = _lib.lib()
+    dq, dk, dk0, dv = (torch.empty_like(q) for _ in range(4))
+    name = "hp_sformer_attention_backward_grouped_masked" if grouped else "hp_sformer_attention_backward_masked"
+    nb = getattr(L, name + "_workspace_bytes")(b, heads, dh, ntok, nj, groups)
+    ws = _ws(nb, q.device)
+    _lib.check(getattr(L, name)(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                                dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), b, heads, dh, ntok, nj, n, groups,
+                                key_mask.data_ptr(), int(bool(mask_patch_queries)), ws.data_ptr(), nb, _st(q)), name)
+    return dq, dk, dk0, dv
+
+
 def attention_backward_grouped(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, groups):
     """attention_backward for short groups (hp_sformer_attention_backward_grouped): n <= 64 tokens per group."""
     L = _lib.lib()
@@ -326,9 +341,11 @@ def layernorm(x, w, b, eps, rows, dim, rows_per_batch=0, batch_stride_rows=0):
     return y
 
 
-def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t, cos_t, prec, pre=None, perm=None, unperm=None):
+def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t, cos_t, prec, pre=None, perm=None, unperm=None,
+                              key_mask=None, mask_patch_queries=False):
     """x + Wo unperm(Attn(perm(pre(LN(x))))) + bo for the token layout [nj | groups x n] of the permuted rows, as
-    _xformer.attention runs it (fp32 attention, with lse).  p = (ln_w, ln_b, wqkv, wo, bo).  -> (x1, saved)."""
+    _xformer.attention runs it (fp32 attention, with lse; key_mask (b, ntok) uint8 in the permuted rows' order selects
+    hp_sformer_attention_lse_masked).  p = (ln_w, ln_b, wqkv, wo, bo).  -> (x1, saved)."""
     L = _lib.lib()
     ln_w, ln_b, wqkv, wo, bo = p
     b, ntok, dim = x.shape
@@ -350,16 +367,22 @@ def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t,
     att = torch.empty(b, ntok, inner, dtype=torch.float32, device=dev)
     lse = torch.empty(b, heads, ntok, dtype=torch.float32, device=dev)
     aws = _ws(L.hp_sformer_attention_workspace_bytes(b, heads, dh), dev)
-    _lib.check(L.hp_sformer_attention_lse(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(), b, heads,
-                                          dh, ntok, nj, n, groups, aws.data_ptr(), st), "hp_sformer_attention_lse")
+    if key_mask is None:
+        _lib.check(L.hp_sformer_attention_lse(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(), b,
+                                              heads, dh, ntok, nj, n, groups, aws.data_ptr(), st), "hp_sformer_attention_lse")
+    else:
+        _lib.check(L.hp_sformer_attention_lse_masked(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(),
+                                                     lse.data_ptr(), b, heads, dh, ntok, nj, n, groups, key_mask.data_ptr(),
+                                                     int(bool(mask_patch_queries)), aws.data_ptr(), st),
+                   "hp_sformer_attention_lse_masked")
     ab = unperm(att) if unperm is not None else att
     x1 = linear(ab.view(rows, inner), wo, bo, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
     return x1, (x, h, q, k, k0, v, att, lse, ab)
 
 
 def prenorm_attention_backward(dx, saved, p, eps, scale, heads, dh, nj, n, groups, sin_t, cos_t, prec, pre_adjoint=None, perm=None,
-                               unperm=None, grouped=False):
-    """dx += d(sublayer input); returns [d ln_w, d ln_b, d wqkv, d wo, d bo]."""
+                               unperm=None, grouped=False, key_mask=None, mask_patch_queries=False):
+    """dx += d(sublayer input); returns [d ln_w, d ln_b, d wqkv, d wo, d bo].  key_mask / mask_patch_queries: the forward's."""
     L = _lib.lib()
     ln_w, _ln_b, wqkv, wo, _bo = p
     x, h, q, k, k0, v, att, lse, ab = saved
@@ -368,8 +391,12 @@ def prenorm_attention_backward(dx, saved, p, eps, scale, heads, dh, nj, n, group
     dab, dwo, dbo = linear_backward(ab.view(rows, inner), dx.view(rows, dim), wo, prec)
     datt = perm(dab.view(b, ntok, inner)) if perm is not None else dab     # the adjoint of unperm is perm
     del dab
-    bwd = attention_backward_grouped if grouped else attention_backward
-    dq, dk, dk0, dv = bwd(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups)
+    if key_mask is None:
+        bwd = attention_backward_grouped if grouped else attention_backward
+        dq, dk, dk0, dv = bwd(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups)
+    else:
+        dq, dk, dk0, dv = attention_backward_masked(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups, key_mask,
+                                                    mask_patch_queries, grouped)
     del datt
     dqkv = torch.empty(rows, 3 * inner, dtype=torch.float32, device=x.device)
     rot_dim = 0 if sin_t is None else sin_t.shape[-1]
@@ -485,12 +512,14 @@ def timesformer_params(m):
 
 
 class TimeSformerFunction(torch.autograd.Function):
-    """video (b, f, c, H, W), *timesformer_params(m) -> (b, 72).  Per layer: time attention (the rotary frame tables, on
-    the transposed token grid: groups = hp*wp patch positions of f tokens), space attention (the axial tables, groups = f
-    frames of hp*wp patches), GEGLU feed-forward; token shift before each when m.shift_tokens."""
+    """video (b, f, c, H, W), module, precision, the frame mask's two (b, 1 + f n) uint8 key masks (natural [cls | f n] and
+    time-permuted [cls | n f] order; both None without a frame mask; not differentiable), *timesformer_params(m) -> (b, 72).
+    Per layer: time attention (the rotary frame tables, on the transposed token grid: groups = hp*wp patch positions of f
+    tokens; every query applies the mask), space attention (the axial tables, groups = f frames of hp*wp patches; only the
+    class query applies it), GEGLU feed-forward; token shift before each when m.shift_tokens."""
 
     @staticmethod
-    def forward(ctx, video, m, prec, *params):
+    def forward(ctx, video, m, prec, mask_nat, mask_time, *params):
         from .transformer import _token_shift
 
         L = _lib.lib()
@@ -517,8 +546,10 @@ class TimeSformerFunction(torch.autograd.Function):
             lp = params[3 + TS_PER_LAYER * i: 3 + TS_PER_LAYER * (i + 1)]
             sc_t, sc_s = _unwrap(time_attn.fn, m.shift_tokens).scale, _unwrap(spatial.fn, m.shift_tokens).scale
             eps = (time_attn.norm.eps, spatial.norm.eps, ff.norm.eps)
-            x, s_t = prenorm_attention_forward(x, lp[0:5], eps[0], sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec, pre, perm, unperm)
-            x, s_s = prenorm_attention_forward(x, lp[5:10], eps[1], sc_s, heads, dh, 1, n, f, sin_s, cos_s, prec, pre)
+            x, s_t = prenorm_attention_forward(x, lp[0:5], eps[0], sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec, pre, perm, unperm,
+                                               key_mask=mask_time, mask_patch_queries=True)
+            x, s_s = prenorm_attention_forward(x, lp[5:10], eps[1], sc_s, heads, dh, 1, n, f, sin_s, cos_s, prec, pre,
+                                               key_mask=mask_nat, mask_patch_queries=False)
             x, s_f = geglu_ff_forward(x, lp[10:16], eps[2], prec, pre)
             saved += [*s_t, *s_s, *s_f]
             consts.append((sc_t, sc_s) + eps)
@@ -527,6 +558,7 @@ class TimeSformerFunction(torch.autograd.Function):
         ctx.geom = (b, f, c, H, W, ps, heads, dh, n, ntok, dim, prec, m.shift_tokens, m.to_out[0].eps)
         ctx.consts = consts
         ctx.nsaved = len(saved)
+        ctx.masks = (mask_nat, mask_time)   # (uint8, no gradient: kept on ctx, not among the saved tensors)
         ctx.save_for_backward(*saved, tokens, x, cls, sin_s, cos_s, sin_t, cos_t, *params)
         return out
 
@@ -548,6 +580,7 @@ class TimeSformerFunction(torch.autograd.Function):
         pre_adj = (lambda t: token_shift_adjoint(t, f)) if shift else None
         perm, unperm = (lambda t: time_perm(t, f, n)), (lambda t: time_unperm(t, f, n))
         grouped = TIME_ATTENTION_BACKWARD == "grouped" and dh in GROUPED_DIM_HEADS
+        mask_nat, mask_time = ctx.masks
         per = 9 + 9 + 3
         for i in reversed(range(len(ctx.consts))):
             sv = saved[per * i: per * (i + 1)]
@@ -556,9 +589,10 @@ class TimeSformerFunction(torch.autograd.Function):
             sc_t, sc_s, e_t, e_s, e_f = ctx.consts[i]
             grads[base + 10: base + 16] = geglu_ff_backward(dx, sv[18:21], lp[10:16], e_f, prec, pre_adj)
             grads[base + 5: base + 10] = prenorm_attention_backward(dx, sv[9:18], lp[5:10], e_s, sc_s, heads, dh, 1, n, f, sin_s, cos_s,
-                                                                    prec, pre_adj)
+                                                                    prec, pre_adj, key_mask=mask_nat, mask_patch_queries=False)
             grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_t, sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec,
-                                                               pre_adj, perm, unperm, grouped=grouped)
+                                                               pre_adj, perm, unperm, grouped=grouped, key_mask=mask_time,
+                                                               mask_patch_queries=True)
         grads[2] = _joint_sum(dx, 1).view(1, dim)      # cls_token (1, dim), shared by the batch
         demb = dx[:, 1:].contiguous().view(b * f * n, dim)
         need_video = ctx.needs_input_grad[0]
@@ -567,7 +601,7 @@ class TimeSformerFunction(torch.autograd.Function):
         if need_video:
             dvideo = torch.empty(b, f, c, H, W, dtype=torch.float32, device=dev)
             _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dvideo.data_ptr(), b, f, c, H, W, ps, _st(dout)), "hp_sformer_unpatchify")
-        return (dvideo, None, None, *grads)
+        return (dvideo, None, None, None, None, *grads)
 
 
 TP_PER_LAYER = 11

@@ -27,11 +27,24 @@ struct ProfScope {
 #define HP_PROF(name, stream) ::hp::ProfScope _hp_prof_scope(name, stream)
 
 // Exact-fp32 launches of sformer_backward.hip that the 16-bit attention backward (sformer_backward16.hip) reuses (dh 32 / 64).
+constexpr int ATTN_JOINT_SPLITS = 32;    // key splits of the joint queries' forward partial records (32 queries x (dh + 2) floats each)
+constexpr int ATTN_GROUPED_MAX_N = 64;   // tokens per group of the grouped attention backward
 constexpr int ATTN_BWD_DQ_SPLITS = 32;   // key splits of the joint queries' dQ partials (32 queries x dh floats each)
 void launch_attn_bwd_joint_keys(const float* ws_dk, const float* ws_dv, float* dK, float* dV, int BH, int Ntok, int dh, int nj, int frames,
                                 hipStream_t st);
 void launch_attn_bwd_dq_joint(const float* Q, const float* K0, const float* V, const float* dout, const float* lse, const float* delta,
                               float* part, float* dQ, int BH, int heads, int dh, int Ntok, int nj, hipStream_t st);
+// Unmasked exact-fp32 launches (dh 16 / 24 / 32 / 64) that the masked attention entries (sformer_masked.hip) share with
+// hp_sformer_attention(_lse) and hp_sformer_attention_backward(_grouped): the patch queries' forward (lse may be null) and dQ
+// when they do not apply the mask, the joint queries' split merges, delta.
+void launch_attention_patch(const float* Q, const float* K, const float* V, float* out, float* lse, int B, int heads, int dh, int Ntok,
+                            int nj, int n, int frames, hipStream_t st);
+void launch_attention_joint_merge(const float* part, float* out, float* lse, int BH, int heads, int dh, int Ntok, int nj, int nsplit,
+                                  hipStream_t st);
+void launch_attn_bwd_delta(const float* out, const float* dout, float* delta, int B, int heads, int dh, int Ntok, hipStream_t st);
+void launch_attn_bwd_dq_patch(const float* Q, const float* K, const float* V, const float* dout, const float* lse, const float* delta,
+                              float* dQ, int BH, int heads, int dh, int Ntok, int nj, int n, int frames, hipStream_t st);
+void launch_attn_bwd_dq_joint_merge(const float* part, float* dQ, int BH, int Ntok, int dh, int nj, int nsplit, hipStream_t st);
 
 // ---- activation tensors stored as fp32 or bf16 (BASELINE configs[2]: bf16 with fp32 accumulators / statistics).  The
 // element type of a tensor is a RUNTIME flag of the call (`half` != 0: bf16), so one kernel serves both layouts: the

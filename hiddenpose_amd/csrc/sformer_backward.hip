@@ -840,7 +840,7 @@ __global__ __launch_bounds__(SB) void k_joint_token_bwd(const float* __restrict_
 static int ln_blocks(long rows) { return (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 1024)); }
 static int colsum_chunks(long rows) { return (int)std::max<long>(1, std::min<long>((rows + 255) / 256, 256)); }
 
-constexpr int GROUPED_MAX_N = 64;   // tokens per group of k_attn_bwd_grouped
+constexpr int GROUPED_MAX_N = ATTN_GROUPED_MAX_N;   // tokens per group of k_attn_bwd_grouped
 // LDS of k_attn_bwd_grouped: two (G n) x dh images + lse, delta of the patch rows; the same for the nj joint rows
 static size_t grouped_lds_bytes(int dh, int nj, int n, int G) {
   return sizeof(float) * ((size_t)G * n * (2 * dh + 2) + (size_t)nj * (2 * dh + 2));
@@ -945,6 +945,24 @@ void launch_attn_bwd_dq_joint(const float* Q, const float* K0, const float* V, c
   const dim3 gj(nsplit, BH);
   if (dh == 64) hipLaunchKernelGGL(k_attn_bwd_dq_joint64, gj, dim3(SB), 0, st, Q, K0, V, dout, lse, delta, part, heads, Ntok, nj);
   else hipLaunchKernelGGL((k_attn_bwd_dq_joint<32>), gj, dim3(SB), 0, st, Q, K0, V, dout, lse, delta, part, heads, Ntok, nj);
+  const long total = (long)BH * nj * dh;
+  hipLaunchKernelGGL(k_attn_bwd_dq_joint_merge, dim3((unsigned)((total + SB - 1) / SB)), dim3(SB), 0, st, part, dQ, BH, Ntok, dh, nj, nsplit);
+}
+// ... and the ones the masked entries (sformer_masked.hip) share with the entries of this file
+void launch_attn_bwd_delta(const float* out, const float* dout, float* delta, int B, int heads, int dh, int Ntok, hipStream_t st) {
+  hipLaunchKernelGGL(k_attn_bwd_delta, dim3(bgrid((long)B * heads * Ntok)), dim3(SB), 0, st, out, dout, delta, B, heads, dh, Ntok);
+}
+void launch_attn_bwd_dq_patch(const float* Q, const float* K, const float* V, const float* dout, const float* lse, const float* delta,
+                              float* dQ, int BH, int heads, int dh, int Ntok, int nj, int n, int frames, hipStream_t st) {
+  const dim3 gq((n + SB - 1) / SB, BH * frames), gq64((n + PB - 1) / PB, BH * frames);
+#define HP_DQ(D) hipLaunchKernelGGL((k_attn_bwd_dq_patch<D>), gq, dim3(SB), 0, st, Q, K, V, dout, lse, delta, dQ, heads, Ntok, nj, n, frames)
+  if (dh == 64) hipLaunchKernelGGL(k_attn_bwd_dq_patch64, gq64, dim3(SB), 0, st, Q, K, V, dout, lse, delta, dQ, heads, Ntok, nj, n, frames);
+  else if (dh == 32) HP_DQ(32);
+  else if (dh == 24) HP_DQ(24);
+  else HP_DQ(16);
+#undef HP_DQ
+}
+void launch_attn_bwd_dq_joint_merge(const float* part, float* dQ, int BH, int Ntok, int dh, int nj, int nsplit, hipStream_t st) {
   const long total = (long)BH * nj * dh;
   hipLaunchKernelGGL(k_attn_bwd_dq_joint_merge, dim3((unsigned)((total + SB - 1) / SB)), dim3(SB), 0, st, part, dQ, BH, Ntok, dh, nj, nsplit);
 }

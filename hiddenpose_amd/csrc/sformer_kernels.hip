@@ -861,7 +861,34 @@ extern "C" int hp_sformer_qkv_prepare(const float* qkv, float* Q, float* K, floa
   return HP_OK;
 }
 
-constexpr int JOINT_SPLITS = 32;
+constexpr int JOINT_SPLITS = ATTN_JOINT_SPLITS;
+
+// The launches the masked entries (sformer_masked.hip) share with the two entries below.
+namespace hp {
+void launch_attention_patch(const float* Q, const float* K, const float* V, float* out, float* lse, int B, int heads, int dh, int Ntok,
+                            int nj, int n, int frames, hipStream_t st) {
+  const dim3 gp((n + 127) / 128, B * heads * frames);
+  float* const part = nullptr;   // (patch mode writes no partial records)
+#define HP_PATCH(KERN) hipLaunchKernelGGL(KERN, gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, nj, n, frames, 0, part, lse)
+  if (lse) {
+    if (dh == 64) HP_PATCH((k_attention64<true>));
+    else if (dh == 32) HP_PATCH((k_attention<32, true>));
+    else if (dh == 24) HP_PATCH((k_attention<24, true>));
+    else HP_PATCH((k_attention<16, true>));
+  } else {
+    if (dh == 64) HP_PATCH((k_attention64<false>));
+    else if (dh == 32) HP_PATCH((k_attention<32>));
+    else if (dh == 24) HP_PATCH((k_attention<24>));
+    else HP_PATCH((k_attention<16>));
+  }
+#undef HP_PATCH
+}
+void launch_attention_joint_merge(const float* part, float* out, float* lse, int BH, int heads, int dh, int Ntok, int nj, int nsplit,
+                                  hipStream_t st) {
+  const int total = BH * nj * dh;
+  hipLaunchKernelGGL(k_attention_joint_merge, dim3((total + 255) / 256), dim3(256), 0, st, part, out, BH, heads, dh, Ntok, nj, nsplit, lse);
+}
+}  // namespace hp
 extern "C" size_t hp_sformer_attention_workspace_bytes(int B, int heads, int dh) {
   return sizeof(float) * (size_t)B * heads * JOINT_SPLITS * 32 * (dh + 2);
 }

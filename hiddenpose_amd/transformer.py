@@ -2,12 +2,19 @@
 feed-forward and optional token shift.
 
 Drop-in for models/transformer.py `TimeSformer(**kwargs)` (:152-257): same constructor keywords, same
-state_dict keys, `forward(video (b, f, c, H, W)) -> (b, 72)`.  Per layer (:251-254): x += TimeAttn(LN(x)) over the f
+state_dict keys, `forward(video (b, f, c, H, W), mask=None) -> (b, 72)`.  Per layer (:251-254): x += TimeAttn(LN(x)) over the f
 tokens that share a patch position; x += SpaceAttn(LN(x)) over the n patches of a frame; x += GEGLU-FF(LN(x)).  In
 both attentions the class token attends to all tokens with un-rotated keys, the patch tokens to [class | their group]
 (:110-141).  All arithmetic is in libhiddenpose_hip.so (see _xformer.py); the '(b n) f' regrouping of the time
 attention is a transposed copy of the token matrix.  Trainable: autograd runs _xformer_autograd.TimeSformerFunction, whose
-backward is a chain of HIP kernels (csrc/sformer_backward.hip).  `mask` (frame masks for ragged clips) is not supported."""
+backward is a chain of HIP kernels (csrc/sformer_backward.hip).
+
+`mask` (b, f) bool, True = the frame is valid (:208-253: a batch of clips of unequal length).  The tokens of a padded frame
+are left out of every soft-max a valid token or the class token takes part in: in the time attention a patch query attends to
+[class | the valid frames of its patch position], in both attentions the class query attends to [class | every valid token];
+the spatial attention's patch queries are not masked (:253 passes only the class mask).  The class key is always attendable,
+so a sample without a valid frame is legal.  The masked kernels are csrc/sformer_masked.hip (exact fp32; an all-True mask
+gives the bits of mask=None).  With shift_tokens the content of padded frames leaks through the shift, as in the reference."""
 from __future__ import annotations
 
 from math import log, pi
@@ -71,25 +78,45 @@ class TimeSformer(nn.Module):
         freqs = torch.cat((freqs, freqs), dim=-1).contiguous()     # models/rotary.py:57-61
         return freqs.sin().contiguous(), freqs.cos().contiguous()
 
+    @staticmethod
+    def _key_masks(mask, video, n):
+        """(b, f) bool frame mask -> the two (b, 1 + f n) uint8 key masks of the attention calls: natural [cls | (f, n)]
+        order (spatial attention) and time-permuted [cls | (n, f)] order (time attention).  Indexing only."""
+        b, f = video.shape[:2]
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or tuple(mask.shape) != (b, f) or mask.device != video.device:
+            got = (f"{mask.dtype} {tuple(mask.shape)} on {mask.device}" if isinstance(mask, torch.Tensor) else type(mask).__name__)
+            raise ValueError(f"TimeSformer.forward: mask must be a bool tensor of shape ({b}, {f}) on {video.device}; got {got}")
+        m8 = mask.to(torch.uint8)
+        nat = torch.ones(b, 1 + f * n, dtype=torch.uint8, device=video.device)
+        nat[:, 1:] = m8[:, :, None].expand(b, f, n).reshape(b, f * n)
+        tim = torch.ones(b, 1 + f * n, dtype=torch.uint8, device=video.device)
+        tim[:, 1:] = m8[:, None, :].expand(b, n, f).reshape(b, n * f)
+        return nat, tim
+
     def forward(self, video, mask=None):
-        """An autograd graph (_xformer_autograd.TimeSformerFunction) is built when grad mode is on, the module is in
+        """mask: None, or a (b, f) bool tensor on video's device, True = valid frame (see the module docstring); anything
+        else raises ValueError.
+        An autograd graph (_xformer_autograd.TimeSformerFunction) is built when grad mode is on, the module is in
         training mode or `video` requires grad, and something (a parameter or `video`) requires grad.  Its forward runs the
         same kernels in the same order as the no-graph path (the output is bit-identical); training needs dropout 0.
         Otherwise the no-graph path runs, launch for launch as an inference-only module would."""
-        assert mask is None, "frame masks are not supported"
         if not video.is_cuda:
             raise _lib.HiddenPoseHipError("TimeSformer.forward needs a tensor on a HIP device; there is no CPU path")
+        masks = (None, None)
+        if mask is not None:
+            ps = self.patch_size
+            masks = self._key_masks(mask, video, (video.shape[-2] // ps) * (video.shape[-1] // ps))
         params = _xa.timesformer_params(self)
         if (torch.is_grad_enabled() and (self.training or video.requires_grad)
                 and (video.requires_grad or any(p.requires_grad for p in params))):
             if self.attn_dropout > 0 or self.ff_dropout > 0:
                 raise _lib.HiddenPoseHipError("TimeSformer training: dropout is not built (attn_dropout / ff_dropout must be 0)")
             with torch.cuda.device(video.device):
-                return _xa.TimeSformerFunction.apply(video.contiguous().float(), self, X.PREC[self.linear_precision], *params)
+                return _xa.TimeSformerFunction.apply(video.contiguous().float(), self, X.PREC[self.linear_precision], *masks, *params)
         with torch.no_grad():
-            return self._forward_nograd(video)
+            return self._forward_nograd(video, *masks)
 
-    def _forward_nograd(self, video):
+    def _forward_nograd(self, video, mask_nat=None, mask_time=None):
         video = video.contiguous().float()
         b, f, c, H, W = video.shape
         ps, heads, dh = self.patch_size, self.heads, self.dim_head
@@ -117,7 +144,8 @@ class TimeSformer(nn.Module):
                 hperm = torch.empty_like(h)
                 hperm[:, :1] = h[:, :1]
                 hperm[:, 1:] = h[:, 1:].view(b, f, n, dim).transpose(1, 2).reshape(b, n * f, dim)
-                att = X.attention(hperm.view(rows, dim), a.to_qkv, b, ntok, heads, dh, 1, f, n, a.scale, sin_t, cos_t, prec)
+                att = X.attention(hperm.view(rows, dim), a.to_qkv, b, ntok, heads, dh, 1, f, n, a.scale, sin_t, cos_t, prec,
+                                  key_mask=mask_time, mask_patch_queries=True)
                 back = torch.empty_like(att)
                 back[:, :1] = att[:, :1]
                 back[:, 1:] = att[:, 1:].view(b, n, f, heads * dh).transpose(1, 2).reshape(b, f * n, heads * dh)
@@ -127,7 +155,8 @@ class TimeSformer(nn.Module):
                 h = X.layernorm(x.view(rows, dim), spatial_attn.norm).view(b, ntok, dim)
                 if self.shift_tokens:
                     h = _token_shift(h, f)
-                att = X.attention(h.view(rows, dim), a.to_qkv, b, ntok, heads, dh, 1, n, f, a.scale, sin_s, cos_s, prec)
+                att = X.attention(h.view(rows, dim), a.to_qkv, b, ntok, heads, dh, 1, n, f, a.scale, sin_s, cos_s, prec,
+                                  key_mask=mask_nat, mask_patch_queries=False)
                 X.linear(att.view(rows, heads * dh), a.to_out[0].weight, a.to_out[0].bias, prec, residual=x.view(rows, dim))
                 # ---- feed-forward
                 m = unwrap(ff.fn)

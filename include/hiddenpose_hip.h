@@ -526,6 +526,42 @@ int hp_sformer_attention_backward_grouped(const float* Q, const float* K, const 
                                           const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B,
                                           int heads, int dh, int Ntok, int num_joints, int patches_per_group, int groups,
                                           void* workspace, size_t workspace_bytes, void* stream);
+/* The exact-fp32 attention entries with a key mask (TimeSformer's frame masks: a batch of clips of unequal length).  Same
+ * arguments as hp_sformer_attention (HP_PRECISION_FP32), hp_sformer_attention_lse, hp_sformer_attention_backward and
+ * hp_sformer_attention_backward_grouped, plus
+ *   key_mask            (B, Ntok) bytes in the call's own token order; nonzero = the token may be attended to.  The bytes of
+ *                       the num_joints joint / class tokens are ignored and treated as 1.
+ *   mask_patch_queries  1: every query applies the mask (a patch query's keys are [joint tokens | the attendable tokens of
+ *                       its group]); 0: only the joint queries do (TimeSformer's spatial attention).
+ * A masked key has probability exactly 0: it is left out of the maximum, the sum, lse (taken over the attendable keys) and
+ * P V, and adds nothing to dQ, dK, dK0, dV.  A group with no attendable token is legal: its queries see the joint tokens.
+ * With an all-nonzero mask every output is bit-equal to the unmasked entry's (same tiling, key splits and order of
+ * accumulation; the mask only selects -FLT_MAX for a score), and the grouped masked backward is bit-equal to the generic
+ * masked backward.  The contract of this section holds: exact fp32, no float atomics, fixed summation order, two calls give
+ * equal bits.  dh 16 / 24 / 32 / 64 (the grouped entry 16 / 24 / 32, patches_per_group <= 64); another dh returns
+ * HP_ERR_UNSUPPORTED.  1 <= num_joints <= 32: num_joints == 0 returns HP_ERR_UNSUPPORTED (an all-masked group would have an
+ * empty key set).  A null key_mask returns HP_ERR_BAD_ARG.  Arguments are checked before any device call.  Workspaces: as
+ * the unmasked entries (hp_sformer_attention_workspace_bytes for the two forward entries). */
+int hp_sformer_attention_masked(const float* Q, const float* K, const float* K0, const float* V, float* out, int B, int heads,
+                                int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
+                                const unsigned char* key_mask, int mask_patch_queries, void* workspace, void* stream);
+int hp_sformer_attention_lse_masked(const float* Q, const float* K, const float* K0, const float* V, float* out, float* lse,
+                                    int B, int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
+                                    const unsigned char* key_mask, int mask_patch_queries, void* workspace, void* stream);
+size_t hp_sformer_attention_backward_masked_workspace_bytes(int B, int heads, int dh, int Ntok, int num_joints, int frames);
+int hp_sformer_attention_backward_masked(const float* Q, const float* K, const float* K0, const float* V, const float* out,
+                                         const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV,
+                                         int B, int heads, int dh, int Ntok, int num_joints, int patches_per_frame,
+                                         int frames, const unsigned char* key_mask, int mask_patch_queries, void* workspace,
+                                         size_t workspace_bytes, void* stream);
+size_t hp_sformer_attention_backward_grouped_masked_workspace_bytes(int B, int heads, int dh, int Ntok, int num_joints,
+                                                                    int groups);
+int hp_sformer_attention_backward_grouped_masked(const float* Q, const float* K, const float* K0, const float* V,
+                                                 const float* out, const float* dout, const float* lse, float* dQ, float* dK,
+                                                 float* dK0, float* dV, int B, int heads, int dh, int Ntok, int num_joints,
+                                                 int patches_per_group, int groups, const unsigned char* key_mask,
+                                                 int mask_patch_queries, void* workspace, size_t workspace_bytes,
+                                                 void* stream);
 /* Transpose of hp_sformer_qkv_prepare: dqkv (B, Ntok, 3 * heads * dh) = [scale R^T(dQ) | R^T(dK) + dK0 | dV], R^T the
  * inverse rotation on the patch tokens' first rot_dim dims (identity on the joint tokens). */
 int hp_sformer_qkv_prepare_backward(const float* dQ, const float* dK, const float* dK0, const float* dV, float* dqkv, int B,

@@ -6,10 +6,14 @@ inputs, same process, median of the timed calls); the device's maxGridSize; and 
 (time attention grid y = B * heads * hp * wp) launches at batch 8.  One JSON line.
 
     python tools/time_xformer_train.py [--steps 5] [--warmup 2] [--ab-calls 20] [--heads 8] [--dim-head 32]
+                                       [--valid-frames K] [--timesformer-only]
 
 --heads / --dim-head set TimeSformer's head split (dim stays 256).  TokenPose-L keeps dim 192 and its 8 heads of 24 unless
 --dim-head is given: then it runs 192 // dim_head heads (3 heads of 64).  The grouped time-attention backward is not built
 for dim_head 64; the A/B is skipped there and the step takes the generic entry.
+--valid-frames K runs the TimeSformer timing with a frame mask (TimeSformer.forward(video, mask)): a prefix mask of K valid
+frames on every sample (K = 16: the all-true mask, i.e. the masked kernels on the unmasked problem).  --timesformer-only
+skips the time-attention A/B, TokenPose-L and the batch-8 launch.
 
 TimeSformer: dim 256, depth 8, 8 heads x 32, 16 frames of 128^2, patch 4, 1 channel, batch 4.
 TokenPose-L: the models/token_config.py geometry (dim 192, 3 x depth 2, 8 heads x 24, 16 keypoints, 4 x 4 patches of a
@@ -50,20 +54,21 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) * 1e3 / steps
 
 
-def head_timing(m, x, R, steps, warmup):
+def head_timing(m, x, R, steps, warmup, **fkw):
+    """fkw: extra keyword arguments of the module's forward (TimeSformer's mask)."""
     m = m.cuda()
 
     def fwd_nograd():
         with torch.no_grad():
-            m.eval()(x)
+            m.eval()(x, **fkw)
 
     state = {}
 
     def fwd_graph():
-        state["y"] = m.train()(x)
+        state["y"] = m.train()(x, **fkw)
 
     def step():
-        y = m.train()(x)
+        y = m.train()(x, **fkw)
         m.zero_grad(set_to_none=True)
         (y * R).sum().backward()
 
@@ -157,6 +162,8 @@ def main():
     ap.add_argument("--ab-calls", type=int, default=20)
     ap.add_argument("--heads", type=int, default=TS_KW["heads"])
     ap.add_argument("--dim-head", type=int, default=None)
+    ap.add_argument("--valid-frames", type=int, default=None, help="TimeSformer: prefix frame mask of K valid frames on every sample")
+    ap.add_argument("--timesformer-only", action="store_true")
     a = ap.parse_args()
     TS_KW.update(heads=a.heads, dim_head=a.dim_head or TS_KW["dim_head"])
     if a.dim_head:
@@ -167,15 +174,24 @@ def main():
     hpt.fill_module(ts, "timesformer.")
     ts = ts.cuda()
     out["geometry"] = {"timesformer": [TS_KW["heads"], TS_KW["dim_head"]], "tokenpose_l": [TP_KW["heads"], TP_KW["dim"] // TP_KW["heads"]]}
-    if TS_KW["dim_head"] in xa.GROUPED_DIM_HEADS:
+    if a.timesformer_only:
+        out["timesformer_time_attention_backward_ab"] = {"skipped": "--timesformer-only"}
+    elif TS_KW["dim_head"] in xa.GROUPED_DIM_HEADS:
         out["timesformer_time_attention_backward_ab"] = time_attention_ab(ts, 4, a.ab_calls)
     else:
         out["timesformer_time_attention_backward_ab"] = {"skipped": "the grouped entry is not built for this dim_head"}
     video = torch.rand(4, 16, 1, 128, 128, generator=torch.Generator().manual_seed(5)).cuda()
     R = torch.randn(4, 72, generator=torch.Generator().manual_seed(6)).cuda()
-    out["timesformer"] = {"batch": 4, "depth": 8, **head_timing(ts, video, R, a.steps, a.warmup)}
+    fkw = {}
+    if a.valid_frames is not None:
+        assert 0 <= a.valid_frames <= TS_KW["num_frames"], "--valid-frames must lie in 0 .. 16"
+        fkw["mask"] = (torch.arange(TS_KW["num_frames"]) < a.valid_frames)[None].expand(4, -1).contiguous().cuda()
+    out["timesformer"] = {"batch": 4, "depth": 8, "valid_frames": a.valid_frames, **head_timing(ts, video, R, a.steps, a.warmup, **fkw)}
     del video, R
     torch.cuda.empty_cache()
+    if a.timesformer_only:
+        print(json.dumps(out))
+        return
     tp = TokenPose_L_base(**TP_KW)
     hpt.fill_module(tp, "tokenpose.")
     feat = torch.rand(8, 128, 64, 64, generator=torch.Generator().manual_seed(5)).cuda()
