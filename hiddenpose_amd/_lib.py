@@ -150,6 +150,11 @@ SIGNATURES = {
     "hp_sformer_attention_backward_masked_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "hp_sformer_attention_backward_masked": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i,
                                                   _vp, _i, _vp, _sz, _vp]),
+    "hp_sformer_attention_masked_p": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "hp_sformer_attention_lse_masked_p": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "hp_sformer_attention_backward_masked_p_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "hp_sformer_attention_backward_masked_p": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i,
+                                                    _vp, _i, _i, _vp, _sz, _vp]),
     "hp_sformer_attention_backward_grouped_masked_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "hp_sformer_attention_backward_grouped_masked": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i,
                                                           _i, _i, _vp, _i, _vp, _sz, _vp]),

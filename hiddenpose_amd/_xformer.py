@@ -9,6 +9,23 @@ import torch
 from . import _lib
 
 PREC = {"fp32": 0, "bf16": 1, "bf16x3": 2, "bf16x6": 3}
+ATTENTION_PREC = {"fp32": 0, "bf16": 1, "fp16": 4}   # HP_PRECISION_* of the attention's patch queries
+
+
+def attention_precisions(module, dim_head, training):
+    """HP_PRECISION_* codes of module.attention_precision and (training only, else 0) module.attention_backward_precision,
+    with NlosPoseSformer's rules: a name outside fp32 / bf16 / fp16 and a 16-bit precision at a dim_head other than 32 / 64
+    raise HiddenPoseHipError."""
+    names = ("attention_precision", "attention_backward_precision") if training else ("attention_precision",)
+    codes = []
+    for name in names:
+        value = getattr(module, name)
+        if value not in ATTENTION_PREC:
+            raise _lib.HiddenPoseHipError(f"{name} {value!r}: one of \"fp32\", \"bf16\", \"fp16\"")
+        codes.append(ATTENTION_PREC[value])
+    if any(codes) and dim_head not in (32, 64):
+        raise _lib.HiddenPoseHipError("bf16 / fp16 attention is built for dim_head 32 and 64 only")
+    return (codes + [0])[:2]
 
 
 def _st(t):
@@ -35,13 +52,14 @@ def layernorm(x2d, norm, rows=None, rows_per_batch=0, batch_stride_rows=0):
 
 
 def attention(h2d, to_qkv, b, ntok, heads, dh, nj, n, frames, scale, sin_t=None, cos_t=None, precision=0, key_mask=None,
-              mask_patch_queries=False):
+              mask_patch_queries=False, attention_precision=0):
     """Multi-head attention over tokens [nj class / joint tokens | frames groups of n tokens]: the class tokens attend
     to every token (keys without rotary embedding), a group's tokens to [class tokens | their group] with the rotary
     tables (n, rot_dim) applied to q and k.  h2d: (b * ntok, dim) normalised input -> (b, ntok, heads * dh).
     key_mask: None (today's call, launch for launch) or a (b, ntok) uint8 tensor in this call's token order, nonzero =
-    attendable (hp_sformer_attention_masked): the class queries leave the masked tokens out, the group queries too when
-    mask_patch_queries."""
+    attendable (hp_sformer_attention_masked_p): the class queries leave the masked tokens out, the group queries too when
+    mask_patch_queries.  attention_precision: HP_PRECISION_* of the group (patch) queries, 0 / 1 (bf16) / 4 (fp16); the 16-bit
+    kernels need dh 32 or 64 and, with a key_mask, mask_patch_queries False.  The class queries are always exact fp32."""
     L = _lib.lib()
     dev = h2d.device
     inner = heads * dh
@@ -55,12 +73,12 @@ def attention(h2d, to_qkv, b, ntok, heads, dh, nj, n, frames, scale, sin_t=None,
     ws = torch.empty(max(1, int(L.hp_sformer_attention_workspace_bytes(b, heads, dh)) // 4), dtype=torch.float32, device=dev)
     if key_mask is None:
         _lib.check(L.hp_sformer_attention(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh, ntok, nj, n,
-                                          frames, 0, ws.data_ptr(), _st(h2d)), "hp_sformer_attention")
+                                          frames, attention_precision, ws.data_ptr(), _st(h2d)), "hp_sformer_attention")
     else:
         check_key_mask(key_mask, b, ntok, dev)
-        _lib.check(L.hp_sformer_attention_masked(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh, ntok,
-                                                 nj, n, frames, key_mask.data_ptr(), int(bool(mask_patch_queries)), ws.data_ptr(),
-                                                 _st(h2d)), "hp_sformer_attention_masked")
+        _lib.check(L.hp_sformer_attention_masked_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh,
+                                                   ntok, nj, n, frames, key_mask.data_ptr(), int(bool(mask_patch_queries)),
+                                                   attention_precision, ws.data_ptr(), _st(h2d)), "hp_sformer_attention_masked_p")
     return att
 
 

@@ -260,6 +260,10 @@ class SformerFunction(torch.autograd.Function):
 # fresh x + sublayer(x) together with what their backward needs; their backward ADDS the sublayer's input gradient into dx
 # (the residual stream's gradient, which already holds d(x + sublayer(x))) and returns the parameter gradients.
 
+FP32_BACKWARD_AFTER_16BIT_FORWARD = ("{} backward: training needs attention_precision = \"fp32\" (the bf16 / fp16 patch attention "
+                                     "has no fp32 backward) or attention_backward_precision = \"bf16\" / \"fp16\"")
+
+
 def gelu_backward(u, dy):
     """du = dy * gelu'(u) (hp_gelu_backward, written over dy)."""
     _lib.check(_lib.lib().hp_gelu_backward(u.data_ptr(), dy.data_ptr(), dy.data_ptr(), u.numel(), _st(u)), "hp_gelu_backward")
@@ -267,11 +271,22 @@ def gelu_backward(u, dy):
 
 
 def attention_backward_masked(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, groups, key_mask, mask_patch_queries,
-                              grouped=False):
+                              grouped=False, precision=0):
     """(dQ, dK, dK0, dV) of the fp32 attention with a key mask (hp_sformer_attention_backward_masked, or its grouped form
-    for n <= 64 tokens per group at dim_head 16 / 24 / 32; the two are bit-equal)."""
+    for n <= 64 tokens per group at dim_head 16 / 24 / 32; the two are bit-equal).  precision 1 (bf16) / 4 (fp16):
+    hp_sformer_attention_backward_masked_p (the patch queries on the 16-bit matrix cores; not grouped, mask_patch_queries False)."""
     L = _lib.lib()
     dq, dk, dk0, dv = (torch.empty_like(q) for _ in range(4))
+    if precision != 0:
+        assert not grouped, "the grouped attention backward is exact fp32"
+        nb = L.hp_sformer_attention_backward_masked_p_workspace_bytes(b, heads, dh, ntok, nj, groups, precision)
+        ws = _ws(nb, q.device)
+        _lib.check(L.hp_sformer_attention_backward_masked_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(),
+                                                            dout.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(),
+                                                            dv.data_ptr(), b, heads, dh, ntok, nj, n, groups, key_mask.data_ptr(),
+                                                            int(bool(mask_patch_queries)), precision, ws.data_ptr(), nb, _st(q)),
+                   "hp_sformer_attention_backward_masked_p")
+        return dq, dk, dk0, dv
     name = "hp_sformer_attention_backward_grouped_masked" if grouped else "hp_sformer_attention_backward_masked"
     nb = getattr(L, name + "_workspace_bytes")(b, heads, dh, ntok, nj, groups)
     ws = _ws(nb, q.device)
@@ -342,10 +357,11 @@ def layernorm(x, w, b, eps, rows, dim, rows_per_batch=0, batch_stride_rows=0):
 
 
 def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t, cos_t, prec, pre=None, perm=None, unperm=None,
-                              key_mask=None, mask_patch_queries=False):
+                              key_mask=None, mask_patch_queries=False, aprec=0):
     """x + Wo unperm(Attn(perm(pre(LN(x))))) + bo for the token layout [nj | groups x n] of the permuted rows, as
-    _xformer.attention runs it (fp32 attention, with lse; key_mask (b, ntok) uint8 in the permuted rows' order selects
-    hp_sformer_attention_lse_masked).  p = (ln_w, ln_b, wqkv, wo, bo).  -> (x1, saved)."""
+    _xformer.attention runs it (with lse; key_mask (b, ntok) uint8 in the permuted rows' order selects
+    hp_sformer_attention_lse_masked).  aprec: HP_PRECISION_* of the patch queries (0; 1 / 4 take the _p entries).
+    p = (ln_w, ln_b, wqkv, wo, bo).  -> (x1, saved)."""
     L = _lib.lib()
     ln_w, ln_b, wqkv, wo, bo = p
     b, ntok, dim = x.shape
@@ -367,9 +383,17 @@ def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t,
     att = torch.empty(b, ntok, inner, dtype=torch.float32, device=dev)
     lse = torch.empty(b, heads, ntok, dtype=torch.float32, device=dev)
     aws = _ws(L.hp_sformer_attention_workspace_bytes(b, heads, dh), dev)
-    if key_mask is None:
+    if key_mask is None and aprec == 0:
         _lib.check(L.hp_sformer_attention_lse(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(), b,
                                               heads, dh, ntok, nj, n, groups, aws.data_ptr(), st), "hp_sformer_attention_lse")
+    elif key_mask is None:
+        _lib.check(L.hp_sformer_attention_lse_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(), b,
+                                                heads, dh, ntok, nj, n, groups, aprec, aws.data_ptr(), st), "hp_sformer_attention_lse_p")
+    elif aprec != 0:
+        _lib.check(L.hp_sformer_attention_lse_masked_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(),
+                                                       lse.data_ptr(), b, heads, dh, ntok, nj, n, groups, key_mask.data_ptr(),
+                                                       int(bool(mask_patch_queries)), aprec, aws.data_ptr(), st),
+                   "hp_sformer_attention_lse_masked_p")
     else:
         _lib.check(L.hp_sformer_attention_lse_masked(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(),
                                                      lse.data_ptr(), b, heads, dh, ntok, nj, n, groups, key_mask.data_ptr(),
@@ -381,8 +405,9 @@ def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t,
 
 
 def prenorm_attention_backward(dx, saved, p, eps, scale, heads, dh, nj, n, groups, sin_t, cos_t, prec, pre_adjoint=None, perm=None,
-                               unperm=None, grouped=False, key_mask=None, mask_patch_queries=False):
-    """dx += d(sublayer input); returns [d ln_w, d ln_b, d wqkv, d wo, d bo].  key_mask / mask_patch_queries: the forward's."""
+                               unperm=None, grouped=False, key_mask=None, mask_patch_queries=False, bprec=0):
+    """dx += d(sublayer input); returns [d ln_w, d ln_b, d wqkv, d wo, d bo].  key_mask / mask_patch_queries: the forward's.
+    bprec: HP_PRECISION_* of the patch queries' part of the attention backward (0; 1 / 4 only without `grouped`)."""
     L = _lib.lib()
     ln_w, _ln_b, wqkv, wo, _bo = p
     x, h, q, k, k0, v, att, lse, ab = saved
@@ -391,12 +416,15 @@ def prenorm_attention_backward(dx, saved, p, eps, scale, heads, dh, nj, n, group
     dab, dwo, dbo = linear_backward(ab.view(rows, inner), dx.view(rows, dim), wo, prec)
     datt = perm(dab.view(b, ntok, inner)) if perm is not None else dab     # the adjoint of unperm is perm
     del dab
-    if key_mask is None:
+    if key_mask is None and bprec != 0:
+        assert not grouped, "the grouped attention backward is exact fp32"
+        dq, dk, dk0, dv = attention_backward(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups, bprec)
+    elif key_mask is None:
         bwd = attention_backward_grouped if grouped else attention_backward
         dq, dk, dk0, dv = bwd(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups)
     else:
         dq, dk, dk0, dv = attention_backward_masked(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups, key_mask,
-                                                    mask_patch_queries, grouped)
+                                                    mask_patch_queries, grouped, bprec)
     del datt
     dqkv = torch.empty(rows, 3 * inner, dtype=torch.float32, device=x.device)
     rot_dim = 0 if sin_t is None else sin_t.shape[-1]
@@ -519,7 +547,9 @@ class TimeSformerFunction(torch.autograd.Function):
     class query applies it), GEGLU feed-forward; token shift before each when m.shift_tokens."""
 
     @staticmethod
-    def forward(ctx, video, m, prec, mask_nat, mask_time, *params):
+    def forward(ctx, video, m, prec, aprec, bprec, mask_nat, mask_time, *params):
+        """aprec, bprec: HP_PRECISION_* of the spatial attention's patch queries, forward and backward (the time attention and
+        the class queries are exact fp32)."""
         from .transformer import _token_shift
 
         L = _lib.lib()
@@ -549,13 +579,14 @@ class TimeSformerFunction(torch.autograd.Function):
             x, s_t = prenorm_attention_forward(x, lp[0:5], eps[0], sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec, pre, perm, unperm,
                                                key_mask=mask_time, mask_patch_queries=True)
             x, s_s = prenorm_attention_forward(x, lp[5:10], eps[1], sc_s, heads, dh, 1, n, f, sin_s, cos_s, prec, pre,
-                                               key_mask=mask_nat, mask_patch_queries=False)
+                                               key_mask=mask_nat, mask_patch_queries=False, aprec=aprec)
             x, s_f = geglu_ff_forward(x, lp[10:16], eps[2], prec, pre)
             saved += [*s_t, *s_s, *s_f]
             consts.append((sc_t, sc_s) + eps)
         cls = layernorm(x, params[-4], params[-3], m.to_out[0].eps, b, dim, 1, ntok)
         out = linear(cls, params[-2], params[-1])
         ctx.geom = (b, f, c, H, W, ps, heads, dh, n, ntok, dim, prec, m.shift_tokens, m.to_out[0].eps)
+        ctx.aprecs = (aprec, bprec)
         ctx.consts = consts
         ctx.nsaved = len(saved)
         ctx.masks = (mask_nat, mask_time)   # (uint8, no gradient: kept on ctx, not among the saved tensors)
@@ -565,6 +596,9 @@ class TimeSformerFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         b, f, c, H, W, ps, heads, dh, n, ntok, dim, prec, shift, eps_out = ctx.geom
+        aprec, bprec = ctx.aprecs
+        if aprec != 0 and bprec == 0:
+            raise _lib.HiddenPoseHipError(FP32_BACKWARD_AFTER_16BIT_FORWARD.format("TimeSformer"))
         L = _lib.lib()
         allt = ctx.saved_tensors
         saved = allt[:ctx.nsaved]
@@ -589,7 +623,8 @@ class TimeSformerFunction(torch.autograd.Function):
             sc_t, sc_s, e_t, e_s, e_f = ctx.consts[i]
             grads[base + 10: base + 16] = geglu_ff_backward(dx, sv[18:21], lp[10:16], e_f, prec, pre_adj)
             grads[base + 5: base + 10] = prenorm_attention_backward(dx, sv[9:18], lp[5:10], e_s, sc_s, heads, dh, 1, n, f, sin_s, cos_s,
-                                                                    prec, pre_adj, key_mask=mask_nat, mask_patch_queries=False)
+                                                                    prec, pre_adj, key_mask=mask_nat, mask_patch_queries=False,
+                                                                    bprec=bprec)
             grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_t, sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec,
                                                                pre_adj, perm, unperm, grouped=grouped, key_mask=mask_time,
                                                                mask_patch_queries=True)
@@ -601,7 +636,7 @@ class TimeSformerFunction(torch.autograd.Function):
         if need_video:
             dvideo = torch.empty(b, f, c, H, W, dtype=torch.float32, device=dev)
             _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dvideo.data_ptr(), b, f, c, H, W, ps, _st(dout)), "hp_sformer_unpatchify")
-        return (dvideo, None, None, None, None, *grads)
+        return (dvideo, None, None, None, None, None, None, *grads)
 
 
 TP_PER_LAYER = 11
@@ -624,7 +659,8 @@ class TokenPoseFunction(torch.autograd.Function):
     x += W2 gelu(W1 LN(x))} over [keypoint tokens | patches] (one all-to-all group, no rotary tables)."""
 
     @staticmethod
-    def forward(ctx, feature, m, prec, *params):
+    def forward(ctx, feature, m, prec, aprec, bprec, *params):
+        """aprec, bprec: HP_PRECISION_* of the attention (every token is a patch query), forward and backward."""
         from . import hip_ops as ops
 
         L = _lib.lib()
@@ -655,7 +691,8 @@ class TokenPoseFunction(torch.autograd.Function):
                     x[:, nk:] = ops.add(x[:, nk:].contiguous(), pos.expand(b, -1, -1).contiguous())
                 a = attn.fn.fn
                 dh = dim // a.heads
-                x, s_a = prenorm_attention_forward(x, lp[0:5], attn.fn.norm.eps, a.scale, a.heads, dh, 0, ntok, 1, None, None, prec)
+                x, s_a = prenorm_attention_forward(x, lp[0:5], attn.fn.norm.eps, a.scale, a.heads, dh, 0, ntok, 1, None, None, prec,
+                                                   aprec=aprec)
                 x, s_f = gelu_ff_forward(x, lp[5:11], ff.fn.norm.eps, prec)
                 saved += [*s_a, *s_f]
                 consts.append((a.scale, a.heads, dh, attn.fn.norm.eps, ff.fn.norm.eps))
@@ -666,6 +703,7 @@ class TokenPoseFunction(torch.autograd.Function):
         out = linear(y, params[-2], params[-1])
         depths = [len(t.layers) for t in (m.transformer1, m.transformer2, m.transformer3)]
         ctx.geom = (b, c, H, W, ps, nk, n, ntok, dim, prec, m.pos_embedding_type, m.mlp_head[0].eps, depths)
+        ctx.aprecs = (aprec, bprec)
         ctx.consts = consts
         ctx.nsaved = len(saved)
         ctx.save_for_backward(*saved, tok, cat, y, *params)
@@ -676,6 +714,9 @@ class TokenPoseFunction(torch.autograd.Function):
         from . import hip_ops as ops
 
         b, c, H, W, ps, nk, n, ntok, dim, prec, pe_type, eps_head, depths = ctx.geom
+        aprec, bprec = ctx.aprecs
+        if aprec != 0 and bprec == 0:
+            raise _lib.HiddenPoseHipError(FP32_BACKWARD_AFTER_16BIT_FORWARD.format("TokenPose"))
         L = _lib.lib()
         allt = ctx.saved_tensors
         saved = allt[:ctx.nsaved]
@@ -706,11 +747,12 @@ class TokenPoseFunction(torch.autograd.Function):
                 lp = params[base: base + TP_PER_LAYER]
                 scale, heads, dh, e_a, e_f = ctx.consts[i]
                 grads[base + 5: base + 11] = gelu_ff_backward(dx, sv[9:13], lp[5:11], e_f, prec)
-                grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_a, scale, heads, dh, 0, ntok, 1, None, None, prec)
+                grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_a, scale, heads, dh, 0, ntok, 1, None, None, prec,
+                                                                   bprec=bprec)
         # token assembly: keypoint_token and the learnable pos_embedding are shared by the batch
-        if ctx.needs_input_grad[3 + 2]:
+        if ctx.needs_input_grad[5 + 2]:
             grads[2] = _joint_sum(dx, nk)
-        if pe_type == "learnable" and ctx.needs_input_grad[3 + 3]:
+        if pe_type == "learnable" and ctx.needs_input_grad[5 + 3]:
             grads[3] = _joint_sum(dx, ntok)
         demb = dx[:, nk:].contiguous().view(b * n, dim)
         need_feat = ctx.needs_input_grad[0]
@@ -719,4 +761,4 @@ class TokenPoseFunction(torch.autograd.Function):
         if need_feat:
             dfeat = torch.empty(b, c, H, W, dtype=torch.float32, device=dev)
             _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dfeat.data_ptr(), b, 1, c, H, W, ps, _st(dout)), "hp_sformer_unpatchify")
-        return (dfeat, None, None, *grads)
+        return (dfeat, None, None, None, None, *grads)

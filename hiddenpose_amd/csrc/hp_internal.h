@@ -45,6 +45,26 @@ void launch_attn_bwd_delta(const float* out, const float* dout, float* delta, in
 void launch_attn_bwd_dq_patch(const float* Q, const float* K, const float* V, const float* dout, const float* lse, const float* delta,
                               float* dQ, int BH, int heads, int dh, int Ntok, int nj, int n, int frames, hipStream_t st);
 void launch_attn_bwd_dq_joint_merge(const float* part, float* dQ, int BH, int Ntok, int dh, int nj, int nsplit, hipStream_t st);
+// What the masked entries at a 16-bit precision (hp_sformer_attention*_masked_p) take from the other two files: the 16-bit patch
+// queries' forward of sformer_kernels.hip (dh 32 / 64, HP_PRECISION_BF16 / _FP16; lse may be null) and the masked joint queries'
+// dQ of sformer_masked.hip.  Their shared argument rule: only the joint / class queries apply the mask.
+void launch_attention_patch16(const float* Q, const float* K, const float* V, float* out, float* lse, int B, int heads, int dh, int Ntok,
+                              int nj, int n, int frames, int precision, hipStream_t st);
+void launch_attn_bwd_dq_joint_masked(const float* Q, const float* K0, const float* V, const float* dout, const float* lse,
+                                     const float* delta, float* part, float* dQ, int BH, int heads, int dh, int Ntok, int nj,
+                                     const unsigned char* key_mask, hipStream_t st);
+inline int attn_masked16_check(const char* who, int num_joints, int mask_patch_queries) {
+  HP_REQUIRE(mask_patch_queries == 0 || mask_patch_queries == 1, "%s: mask_patch_queries must be 0 or 1", who);
+  if (mask_patch_queries) {
+    set_error("%s: mask_patch_queries 1 not built at a 16-bit precision (only the joint / class queries apply the mask there)", who);
+    return HP_ERR_UNSUPPORTED;
+  }
+  if (num_joints == 0) {
+    set_error("%s: num_joints 0 not built (with no joint / class key an all-masked group would have an empty key set)", who);
+    return HP_ERR_UNSUPPORTED;
+  }
+  return HP_OK;
+}
 
 // ---- activation tensors stored as fp32 or bf16 (BASELINE configs[2]: bf16 with fp32 accumulators / statistics).  The
 // element type of a tensor is a RUNTIME flag of the call (`half` != 0: bf16), so one kernel serves both layouts: the

@@ -414,6 +414,78 @@ __global__ __launch_bounds__(BT) void k_attn16_bwd_joint_kv(const float* __restr
   }
 }
 
+// k_attn16_bwd_joint_kv with a key mask (hp_sformer_attention_backward_masked_p), statement for statement: key_mask (B, Ntok),
+// one byte per token, nonzero = attendable.  A patch key (index >= nj) whose byte is 0 has P = 0 for every joint query: it is
+// left out of the sweep, its dK0 row is written as zeros and nothing is added to its dV row.  The joint tokens' bytes are never
+// read.  The same thread / lane pair owns a key and the fmaf chains of an attendable key are the unmasked ones: with an
+// all-nonzero mask the bits are k_attn16_bwd_joint_kv's.  Same grid.
+template <int DH>
+__global__ __launch_bounds__(BT) void k_attn16_bwd_joint_kv_masked(const float* __restrict__ Q, const float* __restrict__ K0,
+                                                                   const float* __restrict__ V, const float* __restrict__ dout,
+                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                   float* __restrict__ dK0, float* __restrict__ dV, int heads,
+                                                                   int Ntok, int nj, const unsigned char* __restrict__ key_mask) {
+  constexpr int PAIR = DH / 32, HD = 32;
+  __shared__ __attribute__((aligned(16))) float Qs[32 * DH];
+  __shared__ __attribute__((aligned(16))) float Gs[32 * DH];
+  __shared__ float Ls[32], Ds[32];
+  const int bh = blockIdx.y, b = bh / heads, head = bh % heads, inner = heads * DH;
+  const long bhN = (long)bh * Ntok;
+  for (int i = threadIdx.x; i < nj * DH; i += BT) {
+    const int r = i / DH, d = i - r * DH;
+    Qs[i] = Q[(bhN + r) * DH + d];
+    Gs[i] = dout[((long)b * Ntok + r) * inner + head * DH + d];
+  }
+  if (threadIdx.x < nj) {
+    Ls[threadIdx.x] = lse[bhN + threadIdx.x];
+    Ds[threadIdx.x] = delta[bhN + threadIdx.x];
+  }
+  __syncthreads();
+  const int d0 = (threadIdx.x % PAIR) * HD;
+  const int kj = blockIdx.x * (BT / PAIR) + threadIdx.x / PAIR;
+  const bool valid = kj < Ntok;
+  const long row = (bhN + min(kj, Ntok - 1)) * DH + d0;   // (a key past the end re-reads the last one: not stored)
+  // does this key take part in the joint queries' soft-max (both lanes of a dh-64 pair share kj)
+  const bool att = kj < nj || key_mask[(long)b * Ntok + min(kj, Ntok - 1)] != 0;
+  float k[HD], v[HD], dk[HD], dv[HD];
+#pragma unroll
+  for (int d = 0; d < HD; ++d) {
+    k[d] = K0[row + d];
+    v[d] = V[row + d];
+    dk[d] = 0.f;
+    dv[d] = 0.f;
+  }
+  for (int r = 0; att && r < nj; ++r) {   // (the pair exchange inside never crosses this condition)
+    const float* q = Qs + r * DH + d0;
+    const float* g = Gs + r * DH + d0;
+    float s = 0.f, dp = 0.f;
+#pragma unroll
+    for (int d = 0; d < HD; ++d) {
+      s = fmaf(k[d], q[d], s);
+      dp = fmaf(v[d], g[d], dp);
+    }
+    if (PAIR == 2) {
+      s = pair_sum16(s);
+      dp = pair_sum16(dp);
+    }
+    const float p = __expf(s - Ls[r]);
+    const float ds = p * (dp - Ds[r]);
+#pragma unroll
+    for (int d = 0; d < HD; ++d) {
+      dv[d] = fmaf(p, g[d], dv[d]);
+      dk[d] = fmaf(ds, q[d], dk[d]);
+    }
+  }
+  if (valid) {
+#pragma unroll
+    for (int d = 0; d < HD; ++d) dK0[row + d] = dk[d];
+    if (att) {
+#pragma unroll
+      for (int d = 0; d < HD; ++d) dV[row + d] += dv[d];
+    }
+  }
+}
+
 }  // namespace hp
 
 using namespace hp;
@@ -425,31 +497,30 @@ extern "C" size_t hp_sformer_attention_backward_p_workspace_bytes(int B, int hea
   return hp_sformer_attention_backward_workspace_bytes(B, heads, dh, Ntok, num_joints, frames);
 }
 
-extern "C" int hp_sformer_attention_backward_p(const float* Q, const float* K, const float* K0, const float* V, const float* out,
-                                               const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B,
-                                               int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
-                                               int precision, void* workspace, size_t workspace_bytes, void* stream) {
-  if (precision == HP_PRECISION_FP32)
-    return hp_sformer_attention_backward(Q, K, K0, V, out, dout, lse, dQ, dK, dK0, dV, B, heads, dh, Ntok, num_joints, patches_per_frame,
-                                         frames, workspace, workspace_bytes, stream);
-  HP_REQUIRE(precision == HP_PRECISION_BF16 || precision == HP_PRECISION_FP16, "hp_sformer_attention_backward_p: precision %d not built",
-             precision);
-  HP_REQUIRE(Q && K && K0 && V && out && dout && lse && dQ && dK && dK0 && dV && workspace,
-             "hp_sformer_attention_backward_p: null argument");
+// The 16-bit backward's launches, shared by hp_sformer_attention_backward_p (key_mask null) and
+// hp_sformer_attention_backward_masked_p (key_mask set: only the joint queries apply it, so the patch queries' three launches and
+// the joint keys' sum are the unmasked ones; the joint queries take k_attn16_bwd_joint_kv_masked and the fp32 path's masked dQ).
+// Every argument check comes before the first device call.
+static int attn_bwd16(const char* who, const float* Q, const float* K, const float* K0, const float* V, const float* out,
+                      const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B, int heads, int dh, int Ntok,
+                      int num_joints, int patches_per_frame, int frames, int precision, const unsigned char* key_mask, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  HP_REQUIRE(precision == HP_PRECISION_BF16 || precision == HP_PRECISION_FP16, "%s: precision %d not built", who, precision);
+  HP_REQUIRE(Q && K && K0 && V && out && dout && lse && dQ && dK && dK0 && dV && workspace, "%s: null argument", who);
   HP_REQUIRE(B > 0 && heads > 0 && frames > 0 && patches_per_frame > 0 && num_joints >= 0 && num_joints <= 32 &&
                  Ntok == num_joints + frames * patches_per_frame,
-             "hp_sformer_attention_backward_p: bad token layout");
+             "%s: bad token layout", who);
   if (dh != 32 && dh != 64) {
-    set_error("hp_sformer_attention_backward_p: dim_head %d not built for the 16-bit backward (32, 64)", dh);
+    set_error("%s: dim_head %d not built for the 16-bit backward (32, 64)", who, dh);
     return HP_ERR_UNSUPPORTED;
   }
   if (workspace_bytes < hp_sformer_attention_backward_p_workspace_bytes(B, heads, dh, Ntok, num_joints, frames, precision)) {
-    set_error("hp_sformer_attention_backward_p: workspace too small");
+    set_error("%s: workspace too small", who);
     return HP_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
   const int BH = B * heads, nj = num_joints, n = patches_per_frame;
-  HP_REQUIRE((long)BH * frames < 65536, "hp_sformer_attention_backward_p: B * heads * frames must stay below 65536");
+  HP_REQUIRE((long)BH * frames < 65536, "%s: B * heads * frames must stay below 65536", who);
   float* delta = (float*)workspace;
   float* ws_dk = delta + (size_t)BH * Ntok;
   float* ws_dv = ws_dk + (size_t)BH * frames * nj * dh;
@@ -486,16 +557,54 @@ extern "C" int hp_sformer_attention_backward_p(const float* Q, const float* K, c
     }
     {
       HP_PROF("sformer_attn_bwd16_joint_kv", st);
-      if (dh == 64) hipLaunchKernelGGL((k_attn16_bwd_joint_kv<64>), dim3((Ntok + 127) / 128, BH), dim3(BT), 0, st, Q, K0, V, dout, lse, delta, dK0, dV, heads, Ntok, nj);
-      else hipLaunchKernelGGL((k_attn16_bwd_joint_kv<32>), dim3((Ntok + 255) / 256, BH), dim3(BT), 0, st, Q, K0, V, dout, lse, delta, dK0, dV, heads, Ntok, nj);
+      const dim3 gj64((Ntok + 127) / 128, BH), gj32((Ntok + 255) / 256, BH);
+      if (key_mask && dh == 64) hipLaunchKernelGGL((k_attn16_bwd_joint_kv_masked<64>), gj64, dim3(BT), 0, st, Q, K0, V, dout, lse, delta, dK0, dV, heads, Ntok, nj, key_mask);
+      else if (key_mask) hipLaunchKernelGGL((k_attn16_bwd_joint_kv_masked<32>), gj32, dim3(BT), 0, st, Q, K0, V, dout, lse, delta, dK0, dV, heads, Ntok, nj, key_mask);
+      else if (dh == 64) hipLaunchKernelGGL((k_attn16_bwd_joint_kv<64>), gj64, dim3(BT), 0, st, Q, K0, V, dout, lse, delta, dK0, dV, heads, Ntok, nj);
+      else hipLaunchKernelGGL((k_attn16_bwd_joint_kv<32>), gj32, dim3(BT), 0, st, Q, K0, V, dout, lse, delta, dK0, dV, heads, Ntok, nj);
     }
     {
       HP_PROF("sformer_attn_bwd_dq_joint", st);
-      launch_attn_bwd_dq_joint(Q, K0, V, dout, lse, delta, part, dQ, BH, heads, dh, Ntok, nj, st);
+      if (key_mask) launch_attn_bwd_dq_joint_masked(Q, K0, V, dout, lse, delta, part, dQ, BH, heads, dh, Ntok, nj, key_mask, st);
+      else launch_attn_bwd_dq_joint(Q, K0, V, dout, lse, delta, part, dQ, BH, heads, dh, Ntok, nj, st);
     }
   } else {
     HP_CHECK_HIP(hipMemsetAsync(dK0, 0, sizeof(float) * (size_t)BH * Ntok * dh, st));   // no joint queries: dK0 is exactly zero
   }
   HP_CHECK_HIP(hipGetLastError());
   return HP_OK;
+}
+
+extern "C" int hp_sformer_attention_backward_p(const float* Q, const float* K, const float* K0, const float* V, const float* out,
+                                               const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV, int B,
+                                               int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
+                                               int precision, void* workspace, size_t workspace_bytes, void* stream) {
+  if (precision == HP_PRECISION_FP32)
+    return hp_sformer_attention_backward(Q, K, K0, V, out, dout, lse, dQ, dK, dK0, dV, B, heads, dh, Ntok, num_joints, patches_per_frame,
+                                         frames, workspace, workspace_bytes, stream);
+  return attn_bwd16("hp_sformer_attention_backward_p", Q, K, K0, V, out, dout, lse, dQ, dK, dK0, dV, B, heads, dh, Ntok, num_joints,
+                    patches_per_frame, frames, precision, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t hp_sformer_attention_backward_masked_p_workspace_bytes(int B, int heads, int dh, int Ntok, int num_joints, int frames,
+                                                                         int precision) {
+  return hp_sformer_attention_backward_p_workspace_bytes(B, heads, dh, Ntok, num_joints, frames, precision);
+}
+
+// hp_sformer_attention_backward_masked with a precision: FP32 forwards to it; BF16 / FP16 are hp_sformer_attention_backward_p's
+// launches with the joint queries' two kernels exchanged for their masked siblings (mask_patch_queries must be 0).
+extern "C" int hp_sformer_attention_backward_masked_p(const float* Q, const float* K, const float* K0, const float* V, const float* out,
+                                                      const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV,
+                                                      int B, int heads, int dh, int Ntok, int num_joints, int patches_per_frame,
+                                                      int frames, const unsigned char* key_mask, int mask_patch_queries, int precision,
+                                                      void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "hp_sformer_attention_backward_masked_p";
+  HP_REQUIRE(key_mask, "%s: null key_mask", who);
+  if (precision == HP_PRECISION_FP32)
+    return hp_sformer_attention_backward_masked(Q, K, K0, V, out, dout, lse, dQ, dK, dK0, dV, B, heads, dh, Ntok, num_joints,
+                                                patches_per_frame, frames, key_mask, mask_patch_queries, workspace, workspace_bytes, stream);
+  HP_REQUIRE(precision == HP_PRECISION_BF16 || precision == HP_PRECISION_FP16, "%s: precision %d not built", who, precision);
+  if (int rc = attn_masked16_check(who, num_joints, mask_patch_queries)) return rc;
+  return attn_bwd16(who, Q, K, K0, V, out, dout, lse, dQ, dK, dK0, dV, B, heads, dh, Ntok, num_joints, patches_per_frame, frames, precision,
+                    key_mask, workspace, workspace_bytes, stream);
 }

@@ -883,6 +883,26 @@ void launch_attention_patch(const float* Q, const float* K, const float* V, floa
   }
 #undef HP_PATCH
 }
+// the 16-bit patch queries (dh 32 / 64, HP_PRECISION_BF16 / _FP16): hp_sformer_attention's launch (lse null) or
+// hp_sformer_attention_lse_p's
+void launch_attention_patch16(const float* Q, const float* K, const float* V, float* out, float* lse, int B, int heads, int dh, int Ntok,
+                              int nj, int n, int frames, int precision, hipStream_t st) {
+  const dim3 gp((n + 127) / 128, B * heads * frames);
+  const bool bf = precision == HP_PRECISION_BF16;
+#define HP_P16(KERN, T, L) hipLaunchKernelGGL((KERN<T, L>), gp, dim3(ST), 0, st, Q, K, V, out, heads, Ntok, nj, n, frames, lse)
+  if (lse) {
+    if (dh == 64 && bf) HP_P16(k_attention_patch_h16_64, __bf16, true);
+    else if (dh == 64) HP_P16(k_attention_patch_h16_64, _Float16, true);
+    else if (bf) HP_P16(k_attention_patch_h16, __bf16, true);
+    else HP_P16(k_attention_patch_h16, _Float16, true);
+  } else {
+    if (dh == 64 && bf) HP_P16(k_attention_patch_h16_64, __bf16, false);
+    else if (dh == 64) HP_P16(k_attention_patch_h16_64, _Float16, false);
+    else if (bf) HP_P16(k_attention_patch_h16, __bf16, false);
+    else HP_P16(k_attention_patch_h16, _Float16, false);
+  }
+#undef HP_P16
+}
 void launch_attention_joint_merge(const float* part, float* out, float* lse, int BH, int heads, int dh, int Ntok, int nj, int nsplit,
                                   hipStream_t st) {
   const int total = BH * nj * dh;

@@ -1016,10 +1016,13 @@ using namespace hp;
 
 // hp_sformer_attention (fp32) and hp_sformer_attention_lse with the key mask: their launches, grids, key splits and merge.  With
 // mask_patch_queries == 0 the patch queries are not masked at all: their launch IS the unmasked kernel.  want_lse false: the
-// inference form.  Every argument check comes before the first device call.
+// inference form.  precision HP_PRECISION_BF16 / _FP16 (the _p entries; mask_patch_queries 0, dh 32 / 64): the patch queries'
+// launch is the unmasked 16-bit patch kernel, the joint queries keep the masked exact-fp32 path.  Every argument check comes
+// before the first device call.
 static int attention_masked(const char* who, const float* Q, const float* K, const float* K0, const float* V, float* out, float* lse,
                             int B, int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
-                            const unsigned char* key_mask, int mask_patch_queries, void* workspace, void* stream, bool want_lse) {
+                            const unsigned char* key_mask, int mask_patch_queries, void* workspace, void* stream, bool want_lse,
+                            int precision = HP_PRECISION_FP32) {
   HP_REQUIRE(key_mask, "%s: null key_mask", who);
   HP_REQUIRE(Q && K && K0 && V && out && workspace && (lse || !want_lse), "%s: null argument", who);
   HP_REQUIRE(B > 0 && heads > 0 && frames > 0 && patches_per_frame > 0 && num_joints >= 0 && num_joints <= 32 &&
@@ -1029,6 +1032,14 @@ static int attention_masked(const char* who, const float* Q, const float* K, con
   if (num_joints == 0) {
     set_error("%s: num_joints 0 not built (with no joint / class key an all-masked group would have an empty key set)", who);
     return HP_ERR_UNSUPPORTED;
+  }
+  const bool p16 = precision != HP_PRECISION_FP32;
+  if (p16) {
+    if (int rc = attn_masked16_check(who, num_joints, mask_patch_queries)) return rc;
+    if (dh != 32 && dh != 64) {
+      set_error("%s: dim_head %d not built for the 16-bit patch attention (32, 64)", who, dh);
+      return HP_ERR_UNSUPPORTED;
+    }
   }
   if (dh != 16 && dh != 24 && dh != 32 && dh != 64) {
     set_error("%s: dim_head %d not built (16, 24, 32, 64)", who, dh);
@@ -1044,7 +1055,9 @@ static int attention_masked(const char* who, const float* Q, const float* K, con
   hipLaunchKernelGGL(KERN, GRID, dim3(ST), 0, st, Q, KK, V, out, heads, Ntok, num_joints, patches_per_frame, frames, MODE, part, LSEP, key_mask)
   {
     HP_PROF("sformer_attention_patch", st);
-    if (!mask_patch_queries) {
+    if (p16) {
+      launch_attention_patch16(Q, K, V, out, lse_out, B, heads, dh, Ntok, num_joints, patches_per_frame, frames, precision, st);
+    } else if (!mask_patch_queries) {
       launch_attention_patch(Q, K, V, out, lse_out, B, heads, dh, Ntok, num_joints, patches_per_frame, frames, st);
     } else if (want_lse) {
       if (dh == 64) HP_ATTM((k_attention64_masked<true>), gp, K, 0, lse);
@@ -1086,10 +1099,41 @@ extern "C" int hp_sformer_attention_lse_masked(const float* Q, const float* K, c
                           frames, key_mask, mask_patch_queries, workspace, stream, true);
 }
 
-// launch_attn_bwd_dq_joint with the key mask (dh 16 / 24 / 32 / 64): the same splits, sub-ranges and ordered merge
-static void launch_attn_bwd_dq_joint_masked(const float* Q, const float* K0, const float* V, const float* dout, const float* lse,
-                                     const float* delta, float* part, float* dQ, int BH, int heads, int dh, int Ntok, int nj,
-                                     const unsigned char* key_mask, hipStream_t st) {
+// The two forward entries with a precision: FP32 forwards to them; BF16 / FP16 exchange the patch queries' launch only.
+#define HP_MASKED_P_HEAD(WHO)                                                                                       \
+  HP_REQUIRE(key_mask, "%s: null key_mask", WHO);                                                                   \
+  HP_REQUIRE(precision == HP_PRECISION_FP32 || precision == HP_PRECISION_BF16 || precision == HP_PRECISION_FP16,    \
+             "%s: precision %d not built", WHO, precision)
+extern "C" int hp_sformer_attention_masked_p(const float* Q, const float* K, const float* K0, const float* V, float* out, int B, int heads,
+                                             int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
+                                             const unsigned char* key_mask, int mask_patch_queries, int precision, void* workspace,
+                                             void* stream) {
+  HP_MASKED_P_HEAD("hp_sformer_attention_masked_p");
+  if (precision == HP_PRECISION_FP32)
+    return hp_sformer_attention_masked(Q, K, K0, V, out, B, heads, dh, Ntok, num_joints, patches_per_frame, frames, key_mask,
+                                       mask_patch_queries, workspace, stream);
+  return attention_masked("hp_sformer_attention_masked_p", Q, K, K0, V, out, nullptr, B, heads, dh, Ntok, num_joints, patches_per_frame,
+                          frames, key_mask, mask_patch_queries, workspace, stream, false, precision);
+}
+
+extern "C" int hp_sformer_attention_lse_masked_p(const float* Q, const float* K, const float* K0, const float* V, float* out, float* lse,
+                                                 int B, int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
+                                                 const unsigned char* key_mask, int mask_patch_queries, int precision, void* workspace,
+                                                 void* stream) {
+  HP_MASKED_P_HEAD("hp_sformer_attention_lse_masked_p");
+  if (precision == HP_PRECISION_FP32)
+    return hp_sformer_attention_lse_masked(Q, K, K0, V, out, lse, B, heads, dh, Ntok, num_joints, patches_per_frame, frames, key_mask,
+                                           mask_patch_queries, workspace, stream);
+  return attention_masked("hp_sformer_attention_lse_masked_p", Q, K, K0, V, out, lse, B, heads, dh, Ntok, num_joints, patches_per_frame,
+                          frames, key_mask, mask_patch_queries, workspace, stream, true, precision);
+}
+#undef HP_MASKED_P_HEAD
+
+// launch_attn_bwd_dq_joint with the key mask (dh 16 / 24 / 32 / 64): the same splits, sub-ranges and ordered merge (shared with the
+// 16-bit masked backward of sformer_backward16.hip)
+void hp::launch_attn_bwd_dq_joint_masked(const float* Q, const float* K0, const float* V, const float* dout, const float* lse,
+                                         const float* delta, float* part, float* dQ, int BH, int heads, int dh, int Ntok, int nj,
+                                         const unsigned char* key_mask, hipStream_t st) {
   const int nsplit = std::max(1, std::min(ATTN_BWD_DQ_SPLITS, (Ntok + 255) / 256));
   const dim3 gj(nsplit, BH);
 #define HP_DQJ(D) hipLaunchKernelGGL((k_attn_bwd_dq_joint_masked<D>), gj, dim3(SB), 0, st, Q, K0, V, dout, lse, delta, part, heads, Ntok, nj, key_mask)

@@ -6,7 +6,12 @@ Patchify 'b c (h p1)(w p2) -> b (h w)(p1 p2 c)' -> Linear -> [keypoint tokens | 
 'sine-full' re-adds it to the patch tokens before every layer but the first, :311-313) -> 3 x Transformer(depth) of
 {x += MHA(LN(x)); x += W2 gelu(W1 LN(x))} -> concat of the keypoint tokens of the three stages -> LayerNorm + Linear
 (+ LayerNorm + Linear) -> heat-maps.  All arithmetic in libhiddenpose_hip.so (_xformer.py); trainable through
-_xformer_autograd.TokenPoseFunction (a HIP backward).  `mask` is not supported."""
+_xformer_autograd.TokenPoseFunction (a HIP backward).  `mask` is not supported.
+
+`attention_precision` / `attention_backward_precision` ("fp32" default, "bf16", "fp16"; NlosPoseSformer's attributes and
+rules) run the all-to-all attention on the 16-bit matrix cores, forward and backward: every token is a patch query here (no
+class queries, one group).  dim // heads must be 32 or 64: the reference's TokenPose-L geometry (8 heads of 24) is refused with
+a 16-bit precision and runs as before otherwise."""
 from __future__ import annotations
 
 import math
@@ -56,7 +61,7 @@ class Transformer(nn.Module):
             nn.ModuleList([_Residual(_PreNorm(dim, _Attention(dim, heads, scale_with_head))),
                            _Residual(_PreNorm(dim, _FeedForward(dim, mlp_dim)))]) for _ in range(depth)])
 
-    def run(self, x, pos, prec):
+    def run(self, x, pos, prec, aprec=0):
         """x (b, ntok, dim) -> new tensor (the input is kept: the three stages' keypoint tokens are concatenated)."""
         b, ntok, dim = x.shape
         rows = b * ntok
@@ -69,7 +74,7 @@ class Transformer(nn.Module):
             dh = dim // a.heads
             h = X.layernorm(x.view(rows, dim), attn.fn.norm)
             # all-to-all attention = one group of ntok tokens, no class tokens, no rotary embedding
-            att = X.attention(h, a.to_qkv, b, ntok, a.heads, dh, 0, ntok, 1, a.scale, None, None, prec)
+            att = X.attention(h, a.to_qkv, b, ntok, a.heads, dh, 0, ntok, 1, a.scale, None, None, prec, attention_precision=aprec)
             X.linear(att.view(rows, dim), a.to_out[0].weight, a.to_out[0].bias, prec, residual=x.view(rows, dim))
             h = X.layernorm(x.view(rows, dim), ff.fn.norm)
             X.gelu_ff(x.view(rows, dim), h, ff.fn.fn.net[0], ff.fn.fn.net[3], prec)
@@ -78,6 +83,9 @@ class Transformer(nn.Module):
 
 class TokenPose_L_base(nn.Module):
     linear_precision = "fp32"
+    # the attention, forward / backward: "fp32" (exact, default), "bf16" or "fp16" (see the module docstring)
+    attention_precision = "fp32"
+    attention_backward_precision = "fp32"
 
     def __init__(self, *, feature_size, patch_size, num_keypoints, dim, depth, heads, mlp_dim, apply_init=False,
                  hidden_heatmap_dim=64 * 6, heatmap_dim=64 * 48, heatmap_size=(64, 48), channels=3, dropout=0.0, emb_dropout=0.0,
@@ -103,6 +111,7 @@ class TokenPose_L_base(nn.Module):
         mk = lambda: Transformer(dim, depth, heads, mlp_dim, dropout, num_keypoints=num_keypoints, all_attn=self.all_attn,
                                  scale_with_head=True)
         self.transformer1, self.transformer2, self.transformer3 = mk(), mk(), mk()
+        self.dim_head = dim // heads
         # (:111-118; the reference's first branch needs an undefined name and a configuration it never takes)
         self.mlp_head = nn.Sequential(nn.LayerNorm(dim * 3), nn.Linear(dim * 3, heatmap_dim))
         nn.init.trunc_normal_(self.keypoint_token, std=0.02)
@@ -136,8 +145,10 @@ class TokenPose_L_base(nn.Module):
                 and (feature.requires_grad or any(p.requires_grad for p in params))):
             if self.dropout > 0 or self.emb_dropout > 0:
                 raise _lib.HiddenPoseHipError("TokenPose training: dropout is not built (dropout / emb_dropout must be 0)")
+            aprec, bprec = X.attention_precisions(self, self.dim_head, training=True)
             with torch.cuda.device(feature.device):
-                return _xa.TokenPoseFunction.apply(feature.contiguous().float(), self, X.PREC[self.linear_precision], *params)
+                return _xa.TokenPoseFunction.apply(feature.contiguous().float(), self, X.PREC[self.linear_precision], aprec, bprec,
+                                                   *params)
         with torch.no_grad():
             return self._forward_nograd(feature)
 
@@ -146,6 +157,7 @@ class TokenPose_L_base(nn.Module):
         b, c, H, W = feature.shape
         nk, dim = self.num_keypoints, self.keypoint_token.shape[-1]
         prec = X.PREC[self.linear_precision]
+        aprec, _ = X.attention_precisions(self, self.dim_head, training=False)
         dev = feature.device
         with torch.cuda.device(dev):
             tok = X.patchify(feature.view(b, 1, c, H, W), self.patch_size[0])
@@ -159,9 +171,9 @@ class TokenPose_L_base(nn.Module):
                 x[:, nk:] = emb
                 x = ops.add(x, self.pos_embedding[:, :n + nk].expand(b, -1, -1).contiguous())
             pos = self.pos_embedding
-            x1 = self.transformer1.run(x, pos, prec)
-            x2 = self.transformer2.run(x1, pos, prec)
-            x3 = self.transformer3.run(x2, pos, prec)
+            x1 = self.transformer1.run(x, pos, prec, aprec)
+            x2 = self.transformer2.run(x1, pos, prec, aprec)
+            x3 = self.transformer3.run(x2, pos, prec, aprec)
             cat = torch.cat((x1[:, :nk], x2[:, :nk], x3[:, :nk]), dim=2).contiguous().view(b * nk, 3 * dim)
             y = X.layernorm(cat, self.mlp_head[0])
             y = X.linear(y, self.mlp_head[1].weight, self.mlp_head[1].bias)

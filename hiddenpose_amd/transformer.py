@@ -14,7 +14,14 @@ are left out of every soft-max a valid token or the class token takes part in: i
 [class | the valid frames of its patch position], in both attentions the class query attends to [class | every valid token];
 the spatial attention's patch queries are not masked (:253 passes only the class mask).  The class key is always attendable,
 so a sample without a valid frame is legal.  The masked kernels are csrc/sformer_masked.hip (exact fp32; an all-True mask
-gives the bits of mask=None).  With shift_tokens the content of padded frames leaks through the shift, as in the reference."""
+gives the bits of mask=None).  With shift_tokens the content of padded frames leaks through the shift, as in the reference.
+
+`attention_precision` / `attention_backward_precision` ("fp32" default, "bf16", "fp16"; NlosPoseSformer's attributes and
+rules: dim_head 32 or 64, a 16-bit forward needs a 16-bit backward, a 16-bit backward takes either forward) put the SPATIAL
+attention's patch queries on the 16-bit matrix cores, forward and backward, with and without `mask`: n patches per frame
+attend to [class | their frame], which is where the attention's work is.  The time attention stays exact fp32 (its groups
+have f + 1 keys: a 32-key MFMA tile would be mostly padding, and its backward is the grouped fp32 kernel), and so do the class
+queries in both attentions (one query over every token, the only query that applies the spatial mask)."""
 from __future__ import annotations
 
 from math import log, pi
@@ -54,6 +61,9 @@ def _token_shift(x, frames, nj=1):
 
 class TimeSformer(nn.Module):
     linear_precision = "fp32"
+    # the spatial attention's patch queries, forward / backward: "fp32" (exact, default), "bf16" or "fp16" (see the module docstring)
+    attention_precision = "fp32"
+    attention_backward_precision = "fp32"
 
     def __init__(self, *, dim, num_frames, num_classes=None, image_size=224, patch_size=16, channels=3, depth=12, heads=8,
                  dim_head=64, attn_dropout=0.0, ff_dropout=0.0, rotary_emb=True, shift_tokens=False):
@@ -111,8 +121,10 @@ class TimeSformer(nn.Module):
                 and (video.requires_grad or any(p.requires_grad for p in params))):
             if self.attn_dropout > 0 or self.ff_dropout > 0:
                 raise _lib.HiddenPoseHipError("TimeSformer training: dropout is not built (attn_dropout / ff_dropout must be 0)")
+            aprec, bprec = X.attention_precisions(self, self.dim_head, training=True)
             with torch.cuda.device(video.device):
-                return _xa.TimeSformerFunction.apply(video.contiguous().float(), self, X.PREC[self.linear_precision], *masks, *params)
+                return _xa.TimeSformerFunction.apply(video.contiguous().float(), self, X.PREC[self.linear_precision], aprec, bprec,
+                                                     *masks, *params)
         with torch.no_grad():
             return self._forward_nograd(video, *masks)
 
@@ -125,6 +137,7 @@ class TimeSformer(nn.Module):
         ntok = 1 + f * n
         dim = self.cls_token.shape[-1]
         prec = X.PREC[self.linear_precision]
+        aprec, _ = X.attention_precisions(self, dh, training=False)
         dev = video.device
         with torch.cuda.device(dev):
             emb = X.linear(X.patchify(video, ps), self.to_patch_embedding.weight, self.to_patch_embedding.bias)
@@ -156,7 +169,7 @@ class TimeSformer(nn.Module):
                 if self.shift_tokens:
                     h = _token_shift(h, f)
                 att = X.attention(h.view(rows, dim), a.to_qkv, b, ntok, heads, dh, 1, n, f, a.scale, sin_s, cos_s, prec,
-                                  key_mask=mask_nat, mask_patch_queries=False)
+                                  key_mask=mask_nat, mask_patch_queries=False, attention_precision=aprec)
                 X.linear(att.view(rows, heads * dh), a.to_out[0].weight, a.to_out[0].bias, prec, residual=x.view(rows, dim))
                 # ---- feed-forward
                 m = unwrap(ff.fn)

@@ -562,6 +562,38 @@ int hp_sformer_attention_backward_grouped_masked(const float* Q, const float* K,
                                                  int patches_per_group, int groups, const unsigned char* key_mask,
                                                  int mask_patch_queries, void* workspace, size_t workspace_bytes,
                                                  void* stream);
+/* The masked entries with a `precision` argument, as the _p entries are to the unmasked ones (TimeSformer's spatial attention
+ * on the 16-bit matrix cores, with a frame mask).  HP_PRECISION_FP32 forwards to hp_sformer_attention_masked / _lse_masked /
+ * _backward_masked: bitwise the same, both values of mask_patch_queries.  HP_PRECISION_BF16 / HP_PRECISION_FP16:
+ *   - mask_patch_queries must be 0: only the joint / class queries apply the mask (1 returns HP_ERR_UNSUPPORTED; there are no
+ *     masked 16-bit patch kernels).  The patch queries run the unmasked 16-bit kernels of hp_sformer_attention /
+ *     hp_sformer_attention_lse_p / hp_sformer_attention_backward_p; the joint queries stay exact fp32 and apply the mask: the
+ *     forward through hp_sformer_attention_lse_masked's joint kernels, dQ through hp_sformer_attention_backward_masked's, dK0
+ *     and their share of dV through the masked sibling of the 16-bit backward's joint kernel.  A masked patch key gets a zero
+ *     dK0 row and nothing from the joint queries in dV; the mask bytes of the joint tokens are ignored.
+ *   - dh 32 or 64 (another dh returns HP_ERR_UNSUPPORTED and names the built set), 1 <= num_joints <= 32 (0 returns
+ *     HP_ERR_UNSUPPORTED), B * heads * frames < 65536 in the backward; another precision value is refused.
+ *   - with an all-nonzero mask out, lse, dQ, dK, dK0 and dV have the bits of hp_sformer_attention / hp_sformer_attention_lse_p /
+ *     hp_sformer_attention_backward_p at the same precision; `out` of hp_sformer_attention_masked_p equals `out` of
+ *     hp_sformer_attention_lse_masked_p; no float atomics, fixed summation order, two calls give equal bits.
+ *   - the rows of Q, K, K0, V, out, dout are read 16 bytes at a time: their base addresses must be 16-byte aligned.
+ * A null key_mask returns HP_ERR_BAD_ARG.  Arguments are checked before any device call.  Workspaces: as the unmasked _p
+ * entries (hp_sformer_attention_workspace_bytes for the two forward entries). */
+int hp_sformer_attention_masked_p(const float* Q, const float* K, const float* K0, const float* V, float* out, int B, int heads,
+                                  int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
+                                  const unsigned char* key_mask, int mask_patch_queries, int precision, void* workspace,
+                                  void* stream);
+int hp_sformer_attention_lse_masked_p(const float* Q, const float* K, const float* K0, const float* V, float* out, float* lse,
+                                      int B, int heads, int dh, int Ntok, int num_joints, int patches_per_frame, int frames,
+                                      const unsigned char* key_mask, int mask_patch_queries, int precision, void* workspace,
+                                      void* stream);
+size_t hp_sformer_attention_backward_masked_p_workspace_bytes(int B, int heads, int dh, int Ntok, int num_joints, int frames,
+                                                              int precision);
+int hp_sformer_attention_backward_masked_p(const float* Q, const float* K, const float* K0, const float* V, const float* out,
+                                           const float* dout, const float* lse, float* dQ, float* dK, float* dK0, float* dV,
+                                           int B, int heads, int dh, int Ntok, int num_joints, int patches_per_frame,
+                                           int frames, const unsigned char* key_mask, int mask_patch_queries, int precision,
+                                           void* workspace, size_t workspace_bytes, void* stream);
 /* Transpose of hp_sformer_qkv_prepare: dqkv (B, Ntok, 3 * heads * dh) = [scale R^T(dQ) | R^T(dK) + dK0 | dV], R^T the
  * inverse rotation on the patch tokens' first rot_dim dims (identity on the joint tokens). */
 int hp_sformer_qkv_prepare_backward(const float* dQ, const float* dK, const float* dK0, const float* dV, float* dqkv, int B,

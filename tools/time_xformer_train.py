@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""TimeSformer and TokenPose-L training-step timing (fp32, seeded inputs): per head the no-graph forward, graph-mode forward,
+"""TimeSformer and TokenPose-L training-step timing (fp32 unless told otherwise, seeded inputs): per head the no-graph forward, graph-mode forward,
 backward, whole step, the library's per-kernel profile of one step and the peak device memory; the A/B of the time
 attention's backward (hp_sformer_attention_backward_grouped against the generic hp_sformer_attention_backward, same saved
 inputs, same process, median of the timed calls); the device's maxGridSize; and whether the no-graph TimeSformer forward
@@ -7,6 +7,7 @@ inputs, same process, median of the timed calls); the device's maxGridSize; and 
 
     python tools/time_xformer_train.py [--steps 5] [--warmup 2] [--ab-calls 20] [--heads 8] [--dim-head 32]
                                        [--valid-frames K] [--timesformer-only]
+                                       [--attention fp32|bf16|fp16] [--attention-backward fp32|bf16|fp16] [--linear fp32|bf16]
 
 --heads / --dim-head set TimeSformer's head split (dim stays 256).  TokenPose-L keeps dim 192 and its 8 heads of 24 unless
 --dim-head is given: then it runs 192 // dim_head heads (3 heads of 64).  The grouped time-attention backward is not built
@@ -14,6 +15,9 @@ for dim_head 64; the A/B is skipped there and the step takes the generic entry.
 --valid-frames K runs the TimeSformer timing with a frame mask (TimeSformer.forward(video, mask)): a prefix mask of K valid
 frames on every sample (K = 16: the all-true mask, i.e. the masked kernels on the unmasked problem).  --timesformer-only
 skips the time-attention A/B, TokenPose-L and the batch-8 launch.
+--attention / --attention-backward / --linear are both heads' attention_precision / attention_backward_precision /
+linear_precision (a 16-bit --attention needs a 16-bit --attention-backward; they need dim_head 32 or 64, so TokenPose-L runs
+them only with --dim-head 32 or 64).  They combine with --valid-frames, --heads and --dim-head.
 
 TimeSformer: dim 256, depth 8, 8 heads x 32, 16 frames of 128^2, patch 4, 1 channel, batch 4.
 TokenPose-L: the models/token_config.py geometry (dim 192, 3 x depth 2, 8 heads x 24, 16 keypoints, 4 x 4 patches of a
@@ -164,15 +168,21 @@ def main():
     ap.add_argument("--dim-head", type=int, default=None)
     ap.add_argument("--valid-frames", type=int, default=None, help="TimeSformer: prefix frame mask of K valid frames on every sample")
     ap.add_argument("--timesformer-only", action="store_true")
+    ap.add_argument("--attention", choices=("fp32", "bf16", "fp16"), default="fp32")
+    ap.add_argument("--attention-backward", choices=("fp32", "bf16", "fp16"), default="fp32")
+    ap.add_argument("--linear", choices=("fp32", "bf16"), default="fp32")
     a = ap.parse_args()
+    if a.attention != "fp32" and a.attention_backward == "fp32":
+        ap.error("--attention bf16 / fp16 needs --attention-backward bf16 / fp16 (the 16-bit patch attention has no fp32 backward)")
     TS_KW.update(heads=a.heads, dim_head=a.dim_head or TS_KW["dim_head"])
     if a.dim_head:
         assert TP_KW["dim"] % a.dim_head == 0, "TokenPose-L: dim 192 must be a multiple of --dim-head"
         TP_KW.update(heads=TP_KW["dim"] // a.dim_head)
-    out = {"precision": "fp32", "time_attention_backward": xa.TIME_ATTENTION_BACKWARD, "max_grid_size": max_grid_size()}
+    out = {"precision": a.linear, "attention": a.attention, "attention_backward": a.attention_backward, "time_attention_backward": xa.TIME_ATTENTION_BACKWARD, "max_grid_size": max_grid_size()}
     ts = TimeSformer(**TS_KW)
     hpt.fill_module(ts, "timesformer.")
     ts = ts.cuda()
+    ts.attention_precision, ts.attention_backward_precision, ts.linear_precision = a.attention, a.attention_backward, a.linear
     out["geometry"] = {"timesformer": [TS_KW["heads"], TS_KW["dim_head"]], "tokenpose_l": [TP_KW["heads"], TP_KW["dim"] // TP_KW["heads"]]}
     if a.timesformer_only:
         out["timesformer_time_attention_backward_ab"] = {"skipped": "--timesformer-only"}
@@ -194,6 +204,7 @@ def main():
         return
     tp = TokenPose_L_base(**TP_KW)
     hpt.fill_module(tp, "tokenpose.")
+    tp.attention_precision, tp.attention_backward_precision, tp.linear_precision = a.attention, a.attention_backward, a.linear
     feat = torch.rand(8, 128, 64, 64, generator=torch.Generator().manual_seed(5)).cuda()
     R = torch.randn(8, 16, 64, 64, generator=torch.Generator().manual_seed(6)).cuda()
     out["tokenpose_l"] = {"batch": 8, **head_timing(tp, feat, R, a.steps, a.warmup)}
