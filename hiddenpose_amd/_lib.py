@@ -164,6 +164,10 @@ SIGNATURES = {
     "hp_linear_backward_weight": (_i, [_fp, _fp, _fp, _fp, C.c_long, _i, _i, _i, _vp, _sz, _vp]),
     "hp_sformer_unpatchify": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
     "hp_sformer_joint_token_backward": (_i, [_fp, _fp, _i, _i, C.c_long, _i, _vp]),
+    "hp_optim_adam_multi_workspace_bytes": (_sz, [_i]),
+    "hp_optim_adam_multi": (_i, [_vp, _i, _d, _d, _d, _d, _vp, _sz, _vp]),
+    "hp_optim_sgd_multi_workspace_bytes": (_sz, [_i]),
+    "hp_optim_sgd_multi": (_i, [_vp, _i, _d, _d, _d, _d, _i, _vp, _sz, _vp]),
 }
 
 
@@ -173,6 +177,18 @@ STATS_SLOTS = 32   # HP_STATS_SLOTS (include/hiddenpose_hip.h): partial statisti
 class ConvDesc(C.Structure):
     """Mirror of `hp_conv_desc` (include/hiddenpose_hip.h)."""
     _fields_ = [(n, C.c_int) for n in ("B", "Di", "Hi", "Wi", "Cin", "Cout", "k", "stride", "pad", "transposed", "precision", "io")]
+
+
+class OptimAdamRec(C.Structure):
+    """Mirror of `hp_optim_adam_rec` (include/hiddenpose_hip.h), 48 bytes."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_long),
+                ("lr_over_bc1", C.c_float), ("inv_sqrt_bc2", C.c_float)]
+
+
+class OptimSgdRec(C.Structure):
+    """Mirror of `hp_optim_sgd_rec` (include/hiddenpose_hip.h), 40 bytes."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("n", C.c_long), ("first_step", C.c_int),
+                ("reserved", C.c_int)]
 
 
 def lib() -> C.CDLL:

@@ -4,7 +4,8 @@ Every function here is one fused stage of the hot path: a ha
 HIP kernel called through the C ABI, wrapped in a torch.autograd.Function so that optimisers
 and torch.distributed stay stock.  `HIP_STAGES` lists the rows; `ATEN_STAGES` names the only
 stock device operator left on the path (Adam).  There is no CPU path: tensors must live on a
-HIP device.
+HIP device.  With HP_OPTIMIZER_IMPL=hip the optimizer is hiddenpose_amd.optimizer.HipAdam and "Adam" moves to
+`HIP_STAGES`.
 """
 from __future__ import annotations
 
@@ -16,6 +17,10 @@ import torch.nn.functional as F
 HIP_STAGES = {"feature_extraction", "lct_forward", "lct_backward", "normalize_feature", "unet3d", "posenet3d_50",
               "softmax_integral", "weighted_mse", "bce_dice"}
 ATEN_STAGES = {"Adam"}
+from .optimizer import hip_optimizer_selected as _hip_optimizer_selected
+
+if _hip_optimizer_selected():   # HP_OPTIMIZER_IMPL=hip: get_optimizer returns HipAdam, the last stage is a HIP kernel as well
+    HIP_STAGES, ATEN_STAGES = HIP_STAGES | {"Adam"}, set()
 
 
 def _need_cuda(x: torch.Tensor, what: str) -> None:

@@ -628,6 +628,59 @@ int hp_sformer_unpatchify(const float* tokens, float* video, int B, int frames, 
 int hp_sformer_joint_token_backward(const float* dx, float* djt, int B, int num_joints, long Ntok, int dim, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Optimizer stage (train.py:131 `optim.Adam(params, lr)`, models/optimizer.py's SGD branch): torch's update rules over a
+ * whole parameter group in ONE kernel launch per call, however many tensors the group has.  Opt-in from Python
+ * (hiddenpose_amd.optimizer.HipAdam / HipSGD); DESIGN 4.6.
+ *
+ * The caller passes a HOST array of `count` records, one per tensor that has a gradient this step; every pointer in a
+ * record is a device pointer to n contiguous fp32 elements (any 4-byte alignment: a gradient may be a view into a flat
+ * bucket).  The records reach the device by one asynchronous copy into `workspace` (caller-owned device memory of at least
+ * hp_optim_*_multi_workspace_bytes(count) bytes, free again when the call's kernel has run) from a pinned staging ring that
+ * the library owns: 8 slots per device, each guarded by an event, so the host waits only when it is 8 calls ahead.  A
+ * steady loop allocates nothing, synchronises no device and reads nothing back.
+ *
+ * Adam (L2 weight decay; no AMSGrad, no decoupled decay), per element:
+ *     g' = g + weight_decay p;  m += (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g'^2;
+ *     p -= lr_over_bc1 * m / (sqrt(v) * inv_sqrt_bc2 + eps)
+ * with lr_over_bc1 = lr / (1 - beta1^t) and inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t) computed by the caller in double from THIS
+ * tensor's step count t (after its increment) and rounded to float: a tensor whose gradient was absent on some steps has
+ * another t than its neighbours, and the learning rate enters only here.
+ * SGD, per element:
+ *     g' = g + weight_decay p;  buf = g' on the tensor's first step (first_step != 0; buf is written, not read), else
+ *     buf = momentum buf + (1 - dampening) g';  p -= lr (g' + momentum buf) with nesterov, else p -= lr buf;
+ *     momentum == 0: p -= lr g', and buf is not touched (it may be NULL).
+ * An element's result bits depend on its values alone: not on the alignment of the pointers, its position in the tensor,
+ * the other records or how a group is split over calls.  g is only read.
+ *
+ * Checked before any device call, HP_ERR_BAD_ARG with a message that names the argument: count < 0, a null record table,
+ * n < 0, a null pointer in a record with n > 0, a null or too small workspace, beta1 or beta2 outside [0, 1), eps < 0,
+ * weight_decay < 0, lr < 0 (Adam: lr_over_bc1 < 0), inv_sqrt_bc2 <= 0, momentum < 0, nesterov without momentum or with
+ * dampening.  count == 0, or n == 0 in every record, succeeds without a launch. */
+typedef struct hp_optim_adam_rec {
+  float* p;
+  const float* g;
+  float* m; /* exp_avg */
+  float* v; /* exp_avg_sq */
+  long n;
+  float lr_over_bc1;
+  float inv_sqrt_bc2;
+} hp_optim_adam_rec;
+typedef struct hp_optim_sgd_rec {
+  float* p;
+  const float* g;
+  float* buf; /* momentum_buffer */
+  long n;
+  int first_step;
+  int reserved; /* 0 */
+} hp_optim_sgd_rec;
+size_t hp_optim_adam_multi_workspace_bytes(int count);
+int hp_optim_adam_multi(const hp_optim_adam_rec* recs, int count, double beta1, double beta2, double eps, double weight_decay,
+                        void* workspace, size_t workspace_bytes, void* stream);
+size_t hp_optim_sgd_multi_workspace_bytes(int count);
+int hp_optim_sgd_multi(const hp_optim_sgd_rec* recs, int count, double lr, double momentum, double dampening,
+                       double weight_decay, int nesterov, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Measurement ingest (utils/nlos_pose_dataloader.py:71-144, utils/loadrealdata.py:6-15): the per-sample
  * CPU work of the reference's Dataset.__getitem__, moved to the device.
  * ---------------------------------------------------------------------- */
