@@ -5,6 +5,16 @@ keywords, same state_dict keys (including the time-attention weights that the re
 but never runs, :66,:133-134), `forward(video (b, f, c, H, W)) -> (b, num_joints, 4, out_dim/4)`.
 All arithmetic runs in libhiddenpose_hip.so (csrc/sformer_kernels.hip, csrc/sformer_backward.hip + the
 fp32 MFMA GEMM and its convolution gradients); autograd trains it through _xformer_autograd.SformerFunction.
+
+Dropout (`attn_dropout` / `ff_dropout`, the reference's keywords) is opt-in by seed, because the HIP path cannot draw from
+torch's global generator: set `dropout_seed` to an int.  It is then ACTIVE while the module is in training mode and one of the
+two probabilities is > 0: every nn.Dropout of the reference's forward is a site whose keep mask is a pure function of
+(dropout_seed, dropout_step, site, element index, p) (Philox4x32-10, hp_dropout_forward), each forward draws its masks and then
+adds 1 to `dropout_step` (also under torch.no_grad(), as torch's dropout follows the training flag alone), setting
+`dropout_step` back replays the same masks, and the backward regenerates them: no mask is stored.  Neither attribute is part
+of the state_dict.  With `dropout_seed` None nothing changes: a training forward with a probability > 0 is refused, the
+no-grad path ignores dropout.  In eval mode nothing is drawn, with or without a seed.  Sites per layer: the spatial attention's
+to_out (attn_dropout), then the feed-forward's hidden activation after the GEGLU (ff_dropout).
 """
 from __future__ import annotations
 
@@ -88,6 +98,8 @@ class NlosPoseSformer(nn.Module):
     # part of the backward on the 16-bit matrix cores (dim_head 32 or 64; the joint queries stay exact fp32), after a forward
     # at either attention_precision
     attention_backward_precision = "fp32"
+    # None: no dropout (training with attn_dropout / ff_dropout > 0 is refused); an int: seeded dropout (module docstring)
+    dropout_seed = None
 
     def __init__(self, *, dim, num_frames, num_joints=24, image_size=224, patch_size=16, channels=2, depth=12, heads=8,
                  dim_head=64, attn_dropout=0.0, ff_dropout=0.0, rotary_emb=True, out_dim=64 * 2 * 3, batch_size=2):
@@ -97,6 +109,7 @@ class NlosPoseSformer(nn.Module):
         _lib.lib()
         self.heads, self.dim_head, self.patch_size, self.num_joints = heads, dim_head, patch_size, num_joints
         self.attn_dropout, self.ff_dropout = attn_dropout, ff_dropout
+        self.dropout_step = 0   # training forwards drawn so far with dropout active (plain attribute, not in the state_dict)
         patch_dim = channels * patch_size ** 2
         self.to_patch_embedding = nn.Linear(patch_dim, dim)
         self.joints_token = nn.Parameter(torch.zeros(1, num_joints, dim))
@@ -111,17 +124,20 @@ class NlosPoseSformer(nn.Module):
     def forward(self, video, mask=None):
         """An autograd graph is built when grad mode is on, the module is in training mode or `video` requires grad, and
         something (a parameter or `video`) requires grad.  Its forward runs the same kernels in the same order as the
-        no-graph path (the output is bit-identical) and keeps what backward needs; backward needs no dropout and
+        no-graph path (the output is bit-identical while dropout is not active) and keeps what backward needs; backward needs
         either attention_precision "fp32" or a 16-bit attention_backward_precision.  Otherwise (eval mode on a plain input, or
-        no_grad) the no-graph path runs, launch for launch as an inference-only module would."""
+        no_grad) the no-graph path runs, launch for launch as an inference-only module would.  With dropout active (module
+        docstring) the forward always goes through SformerFunction, under no_grad too, and adds 1 to dropout_step."""
         assert mask is None, "frame masks are ignored by the reference's attention (:177-179) and not supported"
         if not video.is_cuda:
             raise _lib.HiddenPoseHipError("NlosPoseSformer.forward needs a tensor on a HIP device; there is no CPU path")
         params = _xa.trainable_params(self)
-        if (torch.is_grad_enabled() and (self.training or video.requires_grad)
-                and (video.requires_grad or any(p.requires_grad for p in params))):
-            if self.attn_dropout > 0 or self.ff_dropout > 0:
-                raise _lib.HiddenPoseHipError("NlosPoseSformer training: dropout is not built (attn_dropout / ff_dropout must be 0)")
+        drop = _xa.active_dropout(self, self.attn_dropout, self.ff_dropout)
+        if drop is not None or (torch.is_grad_enabled() and (self.training or video.requires_grad)
+                                and (video.requires_grad or any(p.requires_grad for p in params))):
+            if drop is None and (self.dropout_seed is None or self.training) and (self.attn_dropout > 0 or self.ff_dropout > 0):
+                raise _lib.HiddenPoseHipError("NlosPoseSformer training: dropout is not built without a seed (attn_dropout / "
+                                              "ff_dropout must be 0; set dropout_seed to enable)")
             aprec = {"fp32": 0, "bf16": 1, "fp16": 4}[self.attention_precision]
             if self.attention_backward_precision not in _ATTENTION_PRECISION:
                 raise _lib.HiddenPoseHipError(f"attention_backward_precision {self.attention_backward_precision!r}: one of "
@@ -130,8 +146,11 @@ class NlosPoseSformer(nn.Module):
             if (aprec or bprec) and self.dim_head not in (32, 64):
                 raise _lib.HiddenPoseHipError("bf16 / fp16 attention is built for dim_head 32 and 64 only")
             with torch.cuda.device(video.device):
-                return _xa.SformerFunction.apply(video.contiguous().float(), self, _LINEAR_PRECISION[self.linear_precision], aprec,
-                                                 bprec, *params)
+                out = _xa.SformerFunction.apply(video.contiguous().float(), self, _LINEAR_PRECISION[self.linear_precision], aprec,
+                                                bprec, drop, *params)
+            if drop is not None:
+                self.dropout_step += 1
+            return out
         with torch.no_grad():
             return self._forward_nograd(video)
 

@@ -142,6 +142,10 @@ SIGNATURES = {
     "hp_layernorm_backward": (_i, [_fp, _fp, _fp, _fp, _fp, C.c_long, _i, _fp, C.c_float, _i, C.c_long, _vp, _sz, _vp]),
     "hp_geglu_backward": (_i, [_fp, _fp, _fp, C.c_long, _i, _vp]),
     "hp_gelu_backward": (_i, [_fp, _fp, _fp, C.c_long, _vp]),
+    "hp_dropout_forward": (_i, [_fp, _fp, _fp, C.c_long, C.c_long, _d, C.c_ulonglong, C.c_ulonglong, _vp]),
+    "hp_dropout_mask": (_i, [_vp, C.c_long, C.c_long, _d, C.c_ulonglong, C.c_ulonglong, _vp]),
+    "hp_geglu_backward_dropout": (_i, [_fp, _fp, _fp, C.c_long, _i, _d, C.c_ulonglong, C.c_ulonglong, _vp]),
+    "hp_gelu_backward_dropout": (_i, [_fp, _fp, _fp, C.c_long, _d, C.c_ulonglong, C.c_ulonglong, _vp]),
     "hp_sformer_attention_backward_grouped_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "hp_sformer_attention_backward_grouped": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i,
                                                    _i, _vp, _sz, _vp]),

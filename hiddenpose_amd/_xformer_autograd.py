@@ -4,7 +4,14 @@ what the backward needs, and whose backward is a chain of HIP kernels (include/h
 backward").  PyTorch only allocates, zero-fills and copies.
 
 The op-level helpers (layernorm_backward, linear_backward, geglu_backward, gelu_backward) are written for any row-major
-token matrix; the sublayer helpers (pre-norm attention, GEGLU / GELU feed-forward) serve TimeSformer and TokenPose-L."""
+token matrix; the sublayer helpers (pre-norm attention, GEGLU / GELU feed-forward) serve TimeSformer and TokenPose-L.
+
+Dropout.  Every nn.Dropout of the reference modules is a *site*: its position in the reference's forward
+order.  A Function takes `drop`, None or (seed, step, p, p) with the module's two probabilities; a sublayer helper takes
+`drop`, None or (seed, step, p) for its own sites, and `site`, the index of its first one.  The mask of a site is a pure
+function of (seed, (step << 20) | site, flat element index, p) (hp_dropout_forward), so the backward regenerates it and no
+mask is stored.  A site with p == 0 keeps its index and launches nothing; with drop None the code below is the code that ran
+before dropout was built, launch for launch."""
 from __future__ import annotations
 
 import torch
@@ -18,6 +25,45 @@ def _st(t):
 
 def _ws(nbytes, dev):
     return torch.empty(max(1, (int(nbytes) + 3) // 4), dtype=torch.float32, device=dev)
+
+
+_M64 = (1 << 64) - 1
+
+
+def dropout_stream(step, site):
+    """The Philox stream of dropout site `site` at training step `step`."""
+    return ((int(step) << 20) | int(site)) & _M64
+
+
+def active_dropout(m, p0, p1):
+    """The `drop` tuple (seed, step, p0, p1) of a module's forward, or None: dropout is active when the module is in training
+    mode, one of its two probabilities is > 0 and its dropout_seed is an int."""
+    seed = m.dropout_seed
+    if not m.training or not (p0 > 0 or p1 > 0) or not isinstance(seed, int) or isinstance(seed, bool):
+        return None
+    return (seed, int(m.dropout_step), float(p0), float(p1))
+
+
+def _dropping(drop):
+    return drop is not None and drop[2] > 0
+
+
+def dropout(x, drop, site, addend=None, out=None):
+    """out = dropout(x) (+ addend) over the whole contiguous tensor x (hp_dropout_forward); out defaults to x (in place) and
+    may also be addend.  drop = (seed, step, p)."""
+    seed, step, p = drop
+    out = x if out is None else out
+    _lib.check(_lib.lib().hp_dropout_forward(x.data_ptr(), _lib.ptr(addend), out.data_ptr(), x.numel(), 0, float(p), int(seed) & _M64,
+                                             dropout_stream(step, site), _st(x)), "hp_dropout_forward")
+    return out
+
+
+def dropout_mask(n, first, p, seed, stream, device):
+    """(n,) uint8 keep mask of elements first .. first + n - 1 (hp_dropout_mask): for tests and debugging."""
+    m = torch.empty(n, dtype=torch.uint8, device=device)
+    _lib.check(_lib.lib().hp_dropout_mask(m.data_ptr(), n, first, float(p), int(seed) & _M64, int(stream) & _M64,
+                                          _lib.current_stream_handle(device)), "hp_dropout_mask")
+    return m
 
 
 def linear(x2d, weight, bias=None, precision=0, addend=None):
@@ -66,9 +112,15 @@ def layernorm_backward(x, dy, dx, norm_weight, eps, rows, dim, rows_per_batch=0,
     return dg, db
 
 
-def geglu_backward(u, dg):
+def geglu_backward(u, dg, drop=None, site=0):
+    """du of the GEGLU; with `drop` dg first goes through dropout site `site`'s mask (hp_geglu_backward_dropout)."""
     rows, hid = dg.shape
     du = torch.empty(rows, 2 * hid, dtype=torch.float32, device=u.device)
+    if _dropping(drop):
+        seed, step, p = drop
+        _lib.check(_lib.lib().hp_geglu_backward_dropout(u.data_ptr(), dg.data_ptr(), du.data_ptr(), rows, hid, float(p), int(seed) & _M64,
+                                                        dropout_stream(step, site), _st(u)), "hp_geglu_backward_dropout")
+        return du
     _lib.check(_lib.lib().hp_geglu_backward(u.data_ptr(), dg.data_ptr(), du.data_ptr(), rows, hid, _st(u)), "hp_geglu_backward")
     return du
 
@@ -114,11 +166,15 @@ def trainable_params(m):
 
 
 class SformerFunction(torch.autograd.Function):
-    """video (b, f, c, H, W), module, three precisions, *trainable_params(m) -> (b, num_joints, 4, out_dim / 4)."""
+    """video (b, f, c, H, W), module, three precisions, drop, *trainable_params(m) -> (b, num_joints, 4, out_dim / 4).
+    drop: None or (seed, step, attn_dropout, ff_dropout); sites per layer: 2 i the spatial attention's to_out, 2 i + 1 the
+    feed-forward's hidden activation (the time attention is never run and has no site)."""
 
     @staticmethod
-    def forward(ctx, video, m, prec, aprec, bprec, *params):
+    def forward(ctx, video, m, prec, aprec, bprec, drop, *params):
         """prec, aprec, bprec: HP_PRECISION_* of the Linear layers, the patch attention's forward and the attention backward."""
+        d_attn = None if drop is None else (drop[0], drop[1], drop[2])
+        d_ff = None if drop is None else (drop[0], drop[1], drop[3])
         L = _lib.lib()
         b, f, c, H, W = video.shape
         ps, nj, heads, dh = m.patch_size, m.num_joints, m.heads, m.dim_head
@@ -166,7 +222,11 @@ class SformerFunction(torch.autograd.Function):
             else:
                 _lib.check(L.hp_sformer_attention(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh,
                                                   ntok, nj, n, f, aprec, aws.data_ptr(), st), "hp_sformer_attention")
-            x1 = linear(att.view(rows, inner), wo, bo, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
+            if _dropping(d_attn):
+                x1 = linear(att.view(rows, inner), wo, bo, prec)
+                x1 = dropout(x1, d_attn, 2 * i, addend=x).view(b, ntok, dim)
+            else:
+                x1 = linear(att.view(rows, inner), wo, bo, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
             h2 = torch.empty_like(x)
             _lib.check(L.hp_layernorm_forward(x1.data_ptr(), h2.data_ptr(), rows, dim, ln2_w.data_ptr(), ln2_b.data_ptr(), eps2, 0, 0, st),
                        "hp_layernorm_forward")
@@ -179,6 +239,8 @@ class SformerFunction(torch.autograd.Function):
                 u = linear(h2.view(rows, dim), w1, b1, prec)
                 _lib.check(L.hp_geglu_forward(u.data_ptr(), g.data_ptr(), rows, hid, st), "hp_geglu_forward")
                 del u
+            if _dropping(d_ff):
+                dropout(g, d_ff, 2 * i + 1)     # the saved activation is the dropped one: what W2's gradient needs
             x2 = linear(g, w2, b2, prec, addend=x1.view(rows, dim)).view(b, ntok, dim)
             saved += [x, h1, q, k, k0, v, att, lse, x1, h2, g]
             x = x2
@@ -189,6 +251,7 @@ class SformerFunction(torch.autograd.Function):
         ctx.geom = (b, f, c, H, W, ps, nj, heads, dh, n, ntok, dim, rot_dim, prec, aprec, bprec)
         ctx.consts = [(layer[1].fn.scale, layer[1].norm.eps, layer[2].norm.eps) for layer in m.layers] + [m.to_out[0].eps]
         ctx.depth = len(m.layers)
+        ctx.drops = (d_attn, d_ff)
         ctx.nsaved = len(saved)
         ctx.save_for_backward(*saved, tokens, x, jt, sin_t, cos_t, *params)
         return out.view(b, nj, 4, -1)
@@ -206,6 +269,7 @@ class SformerFunction(torch.autograd.Function):
         dev = dout.device
         st = _st(dout)
         rows, inner = b * ntok, heads * dh
+        d_attn, d_ff = ctx.drops
         grads = [None] * len(params)
         dout = dout.contiguous().view(b * nj, -1)
         # head: LN(x[:, :nj]) -> Linear
@@ -221,14 +285,16 @@ class SformerFunction(torch.autograd.Function):
             d2 = dx.view(rows, dim)
             dg, grads[base + 9], grads[base + 10] = linear_backward(g, d2, w2, prec)
             u = linear(h2.view(rows, dim), w1, b1, prec)
-            du = geglu_backward(u, dg)
+            du = geglu_backward(u, dg, d_ff, 2 * i + 1)
             del u, dg
             dh2, grads[base + 7], grads[base + 8] = linear_backward(h2.view(rows, dim), du, w1, prec)
             del du
             grads[base + 5], grads[base + 6] = layernorm_backward(x1, dh2, dx, ln2_w, eps2, rows, dim)   # dx := dx1
             del dh2
             # attention: x1 = x + Wo att + bo
-            datt, grads[base + 3], grads[base + 4] = linear_backward(att.view(rows, inner), d2, wo, prec)
+            dlin = dropout(d2, d_attn, 2 * i, out=torch.empty_like(d2)) if _dropping(d_attn) else d2
+            datt, grads[base + 3], grads[base + 4] = linear_backward(att.view(rows, inner), dlin, wo, prec)
+            del dlin
             dq, dk, dk0, dv = attention_backward(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, f, bprec)
             del datt
             dqkv = torch.empty(rows, 3 * inner, dtype=torch.float32, device=dev)
@@ -252,7 +318,7 @@ class SformerFunction(torch.autograd.Function):
         if need_video:
             dvideo = torch.empty(b, f, c, H, W, dtype=torch.float32, device=dev)
             _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dvideo.data_ptr(), b, f, c, H, W, ps, st), "hp_sformer_unpatchify")
-        return (dvideo, None, None, None, None, *grads)
+        return (dvideo, None, None, None, None, None, *grads)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -264,8 +330,14 @@ FP32_BACKWARD_AFTER_16BIT_FORWARD = ("{} backward: training needs attention_prec
                                      "has no fp32 backward) or attention_backward_precision = \"bf16\" / \"fp16\"")
 
 
-def gelu_backward(u, dy):
-    """du = dy * gelu'(u) (hp_gelu_backward, written over dy)."""
+def gelu_backward(u, dy, drop=None, site=0):
+    """du = dy * gelu'(u) (hp_gelu_backward, written over dy); with `drop` dy first goes through dropout site `site`'s mask
+    (hp_gelu_backward_dropout)."""
+    if _dropping(drop):
+        seed, step, p = drop
+        _lib.check(_lib.lib().hp_gelu_backward_dropout(u.data_ptr(), dy.data_ptr(), dy.data_ptr(), u.numel(), float(p), int(seed) & _M64,
+                                                       dropout_stream(step, site), _st(u)), "hp_gelu_backward_dropout")
+        return dy
     _lib.check(_lib.lib().hp_gelu_backward(u.data_ptr(), dy.data_ptr(), dy.data_ptr(), u.numel(), _st(u)), "hp_gelu_backward")
     return dy
 
@@ -357,11 +429,11 @@ def layernorm(x, w, b, eps, rows, dim, rows_per_batch=0, batch_stride_rows=0):
 
 
 def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t, cos_t, prec, pre=None, perm=None, unperm=None,
-                              key_mask=None, mask_patch_queries=False, aprec=0):
+                              key_mask=None, mask_patch_queries=False, aprec=0, drop=None, site=0):
     """x + Wo unperm(Attn(perm(pre(LN(x))))) + bo for the token layout [nj | groups x n] of the permuted rows, as
     _xformer.attention runs it (with lse; key_mask (b, ntok) uint8 in the permuted rows' order selects
     hp_sformer_attention_lse_masked).  aprec: HP_PRECISION_* of the patch queries (0; 1 / 4 take the _p entries).
-    p = (ln_w, ln_b, wqkv, wo, bo).  -> (x1, saved)."""
+    p = (ln_w, ln_b, wqkv, wo, bo).  drop / site: dropout on to_out's output, before the residual.  -> (x1, saved)."""
     L = _lib.lib()
     ln_w, ln_b, wqkv, wo, bo = p
     b, ntok, dim = x.shape
@@ -400,12 +472,16 @@ def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t,
                                                      int(bool(mask_patch_queries)), aws.data_ptr(), st),
                    "hp_sformer_attention_lse_masked")
     ab = unperm(att) if unperm is not None else att
-    x1 = linear(ab.view(rows, inner), wo, bo, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
+    if _dropping(drop):
+        x1 = linear(ab.view(rows, inner), wo, bo, prec)
+        x1 = dropout(x1, drop, site, addend=x).view(b, ntok, dim)
+    else:
+        x1 = linear(ab.view(rows, inner), wo, bo, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
     return x1, (x, h, q, k, k0, v, att, lse, ab)
 
 
 def prenorm_attention_backward(dx, saved, p, eps, scale, heads, dh, nj, n, groups, sin_t, cos_t, prec, pre_adjoint=None, perm=None,
-                               unperm=None, grouped=False, key_mask=None, mask_patch_queries=False, bprec=0):
+                               unperm=None, grouped=False, key_mask=None, mask_patch_queries=False, bprec=0, drop=None, site=0):
     """dx += d(sublayer input); returns [d ln_w, d ln_b, d wqkv, d wo, d bo].  key_mask / mask_patch_queries: the forward's.
     bprec: HP_PRECISION_* of the patch queries' part of the attention backward (0; 1 / 4 only without `grouped`)."""
     L = _lib.lib()
@@ -413,7 +489,11 @@ def prenorm_attention_backward(dx, saved, p, eps, scale, heads, dh, nj, n, group
     x, h, q, k, k0, v, att, lse, ab = saved
     b, ntok, dim = x.shape
     rows, inner = b * ntok, heads * dh
-    dab, dwo, dbo = linear_backward(ab.view(rows, inner), dx.view(rows, dim), wo, prec)
+    dlin = dx.view(rows, dim)
+    if _dropping(drop):
+        dlin = dropout(dlin, drop, site, out=torch.empty_like(dlin))
+    dab, dwo, dbo = linear_backward(ab.view(rows, inner), dlin, wo, prec)
+    del dlin
     datt = perm(dab.view(b, ntok, inner)) if perm is not None else dab     # the adjoint of unperm is perm
     del dab
     if key_mask is None and bprec != 0:
@@ -443,8 +523,9 @@ def prenorm_attention_backward(dx, saved, p, eps, scale, heads, dh, nj, n, group
     return [dg, db, dwqkv, dwo, dbo]
 
 
-def geglu_ff_forward(x, p, eps, prec, pre=None):
-    """x + W2 GEGLU(W1 pre(LN(x)) + b1) + b2 as _xformer.geglu_ff runs it.  p = (ln_w, ln_b, w1, b1, w2, b2)."""
+def geglu_ff_forward(x, p, eps, prec, pre=None, drop=None, site=0):
+    """x + W2 GEGLU(W1 pre(LN(x)) + b1) + b2 as _xformer.geglu_ff runs it.  p = (ln_w, ln_b, w1, b1, w2, b2).  drop / site:
+    dropout on the hidden activation (in place: the saved g is the dropped one, what W2's gradient needs)."""
     L = _lib.lib()
     ln_w, ln_b, w1, b1, w2, b2 = p
     b, ntok, dim = x.shape
@@ -462,11 +543,13 @@ def geglu_ff_forward(x, p, eps, prec, pre=None):
         u = linear(h.view(rows, dim), w1, b1, prec)
         _lib.check(L.hp_geglu_forward(u.data_ptr(), g.data_ptr(), rows, hid, st), "hp_geglu_forward")
         del u
+    if _dropping(drop):
+        dropout(g, drop, site)
     x1 = linear(g, w2, b2, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
     return x1, (x, h, g)
 
 
-def geglu_ff_backward(dx, saved, p, eps, prec, pre_adjoint=None):
+def geglu_ff_backward(dx, saved, p, eps, prec, pre_adjoint=None, drop=None, site=0):
     """dx += d(sublayer input); returns [d ln_w, d ln_b, d w1, d b1, d w2, d b2].  u is recomputed from the saved input."""
     ln_w, _ln_b, w1, b1, w2, _b2 = p
     x, h, g = saved
@@ -474,7 +557,7 @@ def geglu_ff_backward(dx, saved, p, eps, prec, pre_adjoint=None):
     rows = b * ntok
     dg, dw2, db2 = linear_backward(g, dx.view(rows, dim), w2, prec)
     u = linear(h.view(rows, dim), w1, b1, prec)
-    du = geglu_backward(u, dg)
+    du = geglu_backward(u, dg, drop, site)
     del u, dg
     dh_, dw1, db1 = linear_backward(h.view(rows, dim), du, w1, prec)
     del du
@@ -485,8 +568,9 @@ def geglu_ff_backward(dx, saved, p, eps, prec, pre_adjoint=None):
     return [dg_, db_, dw1, db1, dw2, db2]
 
 
-def gelu_ff_forward(x, p, eps, prec):
-    """x + W2 gelu(W1 LN(x) + b1) + b2 as _xformer.gelu_ff runs it, with the GELU out of place (u is kept)."""
+def gelu_ff_forward(x, p, eps, prec, drop=None, site=0):
+    """x + W2 gelu(W1 LN(x) + b1) + b2 as _xformer.gelu_ff runs it, with the GELU out of place (u is kept).  drop: dropout on the
+    hidden activation (site `site`, in place: the saved a is the dropped one) and on W2's output (site + 1)."""
     ln_w, ln_b, w1, b1, w2, b2 = p
     b, ntok, dim = x.shape
     rows = b * ntok
@@ -494,17 +578,26 @@ def gelu_ff_forward(x, p, eps, prec):
     u = linear(h, w1, b1, prec)
     a = torch.empty_like(u)
     _lib.check(_lib.lib().hp_gelu_forward(u.data_ptr(), a.data_ptr(), u.numel(), _st(x)), "hp_gelu_forward")
-    x1 = linear(a, w2, b2, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
+    if _dropping(drop):
+        dropout(a, drop, site)
+        x1 = linear(a, w2, b2, prec)
+        x1 = dropout(x1, drop, site + 1, addend=x).view(b, ntok, dim)
+    else:
+        x1 = linear(a, w2, b2, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
     return x1, (x, h, u, a)
 
 
-def gelu_ff_backward(dx, saved, p, eps, prec):
+def gelu_ff_backward(dx, saved, p, eps, prec, drop=None, site=0):
     ln_w, _ln_b, w1, _b1, w2, _b2 = p
     x, h, u, a = saved
     b, ntok, dim = x.shape
     rows = b * ntok
-    da, dw2, db2 = linear_backward(a, dx.view(rows, dim), w2, prec)
-    du = gelu_backward(u, da)
+    dlin = dx.view(rows, dim)
+    if _dropping(drop):
+        dlin = dropout(dlin, drop, site + 1, out=torch.empty_like(dlin))
+    da, dw2, db2 = linear_backward(a, dlin, w2, prec)
+    del dlin
+    du = gelu_backward(u, da, drop, site)
     dh_, dw1, db1 = linear_backward(h, du, w1, prec)
     del du
     dg_, db_ = layernorm_backward(x, dh_, dx, ln_w, eps, rows, dim)
@@ -541,13 +634,15 @@ def timesformer_params(m):
 
 class TimeSformerFunction(torch.autograd.Function):
     """video (b, f, c, H, W), module, precision, the frame mask's two (b, 1 + f n) uint8 key masks (natural [cls | f n] and
-    time-permuted [cls | n f] order; both None without a frame mask; not differentiable), *timesformer_params(m) -> (b, 72).
+    time-permuted [cls | n f] order; both None without a frame mask; not differentiable), drop (None or (seed, step,
+    attn_dropout, ff_dropout); sites per layer: 3 i the time attention's to_out, on the un-permuted rows, 3 i + 1 the spatial
+    attention's, 3 i + 2 the feed-forward's hidden activation), *timesformer_params(m) -> (b, 72).
     Per layer: time attention (the rotary frame tables, on the transposed token grid: groups = hp*wp patch positions of f
     tokens; every query applies the mask), space attention (the axial tables, groups = f frames of hp*wp patches; only the
     class query applies it), GEGLU feed-forward; token shift before each when m.shift_tokens."""
 
     @staticmethod
-    def forward(ctx, video, m, prec, aprec, bprec, mask_nat, mask_time, *params):
+    def forward(ctx, video, m, prec, aprec, bprec, mask_nat, mask_time, drop, *params):
         """aprec, bprec: HP_PRECISION_* of the spatial attention's patch queries, forward and backward (the time attention and
         the class queries are exact fp32)."""
         from .transformer import _token_shift
@@ -572,15 +667,17 @@ class TimeSformerFunction(torch.autograd.Function):
         pre = (lambda t: _token_shift(t, f)) if m.shift_tokens else None
         perm, unperm = (lambda t: time_perm(t, f, n)), (lambda t: time_unperm(t, f, n))
         saved, consts = [], []
+        d_attn = None if drop is None else (drop[0], drop[1], drop[2])
+        d_ff = None if drop is None else (drop[0], drop[1], drop[3])
         for i, (time_attn, spatial, ff) in enumerate(m.layers):
             lp = params[3 + TS_PER_LAYER * i: 3 + TS_PER_LAYER * (i + 1)]
             sc_t, sc_s = _unwrap(time_attn.fn, m.shift_tokens).scale, _unwrap(spatial.fn, m.shift_tokens).scale
             eps = (time_attn.norm.eps, spatial.norm.eps, ff.norm.eps)
             x, s_t = prenorm_attention_forward(x, lp[0:5], eps[0], sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec, pre, perm, unperm,
-                                               key_mask=mask_time, mask_patch_queries=True)
+                                               key_mask=mask_time, mask_patch_queries=True, drop=d_attn, site=3 * i)
             x, s_s = prenorm_attention_forward(x, lp[5:10], eps[1], sc_s, heads, dh, 1, n, f, sin_s, cos_s, prec, pre,
-                                               key_mask=mask_nat, mask_patch_queries=False, aprec=aprec)
-            x, s_f = geglu_ff_forward(x, lp[10:16], eps[2], prec, pre)
+                                               key_mask=mask_nat, mask_patch_queries=False, aprec=aprec, drop=d_attn, site=3 * i + 1)
+            x, s_f = geglu_ff_forward(x, lp[10:16], eps[2], prec, pre, drop=d_ff, site=3 * i + 2)
             saved += [*s_t, *s_s, *s_f]
             consts.append((sc_t, sc_s) + eps)
         cls = layernorm(x, params[-4], params[-3], m.to_out[0].eps, b, dim, 1, ntok)
@@ -588,6 +685,7 @@ class TimeSformerFunction(torch.autograd.Function):
         ctx.geom = (b, f, c, H, W, ps, heads, dh, n, ntok, dim, prec, m.shift_tokens, m.to_out[0].eps)
         ctx.aprecs = (aprec, bprec)
         ctx.consts = consts
+        ctx.drops = (d_attn, d_ff)
         ctx.nsaved = len(saved)
         ctx.masks = (mask_nat, mask_time)   # (uint8, no gradient: kept on ctx, not among the saved tensors)
         ctx.save_for_backward(*saved, tokens, x, cls, sin_s, cos_s, sin_t, cos_t, *params)
@@ -615,19 +713,20 @@ class TimeSformerFunction(torch.autograd.Function):
         perm, unperm = (lambda t: time_perm(t, f, n)), (lambda t: time_unperm(t, f, n))
         grouped = TIME_ATTENTION_BACKWARD == "grouped" and dh in GROUPED_DIM_HEADS
         mask_nat, mask_time = ctx.masks
+        d_attn, d_ff = ctx.drops
         per = 9 + 9 + 3
         for i in reversed(range(len(ctx.consts))):
             sv = saved[per * i: per * (i + 1)]
             base = 3 + TS_PER_LAYER * i
             lp = params[base: base + TS_PER_LAYER]
             sc_t, sc_s, e_t, e_s, e_f = ctx.consts[i]
-            grads[base + 10: base + 16] = geglu_ff_backward(dx, sv[18:21], lp[10:16], e_f, prec, pre_adj)
+            grads[base + 10: base + 16] = geglu_ff_backward(dx, sv[18:21], lp[10:16], e_f, prec, pre_adj, drop=d_ff, site=3 * i + 2)
             grads[base + 5: base + 10] = prenorm_attention_backward(dx, sv[9:18], lp[5:10], e_s, sc_s, heads, dh, 1, n, f, sin_s, cos_s,
                                                                     prec, pre_adj, key_mask=mask_nat, mask_patch_queries=False,
-                                                                    bprec=bprec)
+                                                                    bprec=bprec, drop=d_attn, site=3 * i + 1)
             grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_t, sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec,
                                                                pre_adj, perm, unperm, grouped=grouped, key_mask=mask_time,
-                                                               mask_patch_queries=True)
+                                                               mask_patch_queries=True, drop=d_attn, site=3 * i)
         grads[2] = _joint_sum(dx, 1).view(1, dim)      # cls_token (1, dim), shared by the batch
         demb = dx[:, 1:].contiguous().view(b * f * n, dim)
         need_video = ctx.needs_input_grad[0]
@@ -636,7 +735,7 @@ class TimeSformerFunction(torch.autograd.Function):
         if need_video:
             dvideo = torch.empty(b, f, c, H, W, dtype=torch.float32, device=dev)
             _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dvideo.data_ptr(), b, f, c, H, W, ps, _st(dout)), "hp_sformer_unpatchify")
-        return (dvideo, None, None, None, None, None, None, *grads)
+        return (dvideo, None, None, None, None, None, None, None, *grads)
 
 
 TP_PER_LAYER = 11
@@ -655,12 +754,17 @@ def tokenpose_params(m):
 
 
 class TokenPoseFunction(torch.autograd.Function):
-    """feature (b, c, H, W), *tokenpose_params(m) -> (b, num_keypoints, h_hm, w_hm).  Three stages of {x += MHA(LN(x));
-    x += W2 gelu(W1 LN(x))} over [keypoint tokens | patches] (one all-to-all group, no rotary tables)."""
+    """feature (b, c, H, W), module, three precisions, drop, *tokenpose_params(m) -> (b, num_keypoints, h_hm, w_hm).  Three
+    stages of {x += MHA(LN(x)); x += W2 gelu(W1 LN(x))} over [keypoint tokens | patches] (one all-to-all group, no rotary
+    tables).  drop: None or (seed, step, dropout, emb_dropout); site 0 is the assembled token matrix (emb_dropout), then per
+    layer l (counted through the three stages) 1 + 3 l the attention's to_out, 2 + 3 l the hidden activation after the GELU,
+    3 + 3 l the feed-forward's output (all `dropout`)."""
 
     @staticmethod
-    def forward(ctx, feature, m, prec, aprec, bprec, *params):
+    def forward(ctx, feature, m, prec, aprec, bprec, drop, *params):
         """aprec, bprec: HP_PRECISION_* of the attention (every token is a patch query), forward and backward."""
+        d_lay = None if drop is None else (drop[0], drop[1], drop[2])
+        d_emb = None if drop is None else (drop[0], drop[1], drop[3])
         from . import hip_ops as ops
 
         L = _lib.lib()
@@ -681,6 +785,8 @@ class TokenPoseFunction(torch.autograd.Function):
             x[:, nk:] = emb
             x = ops.add(x, pos[:, :n + nk].expand(b, -1, -1).contiguous())
         del emb
+        if _dropping(d_emb):
+            dropout(x, d_emb, 0)
         saved, consts, outs = [], [], []
         i = 0
         for t in (m.transformer1, m.transformer2, m.transformer3):
@@ -692,8 +798,8 @@ class TokenPoseFunction(torch.autograd.Function):
                 a = attn.fn.fn
                 dh = dim // a.heads
                 x, s_a = prenorm_attention_forward(x, lp[0:5], attn.fn.norm.eps, a.scale, a.heads, dh, 0, ntok, 1, None, None, prec,
-                                                   aprec=aprec)
-                x, s_f = gelu_ff_forward(x, lp[5:11], ff.fn.norm.eps, prec)
+                                                   aprec=aprec, drop=d_lay, site=1 + 3 * i)
+                x, s_f = gelu_ff_forward(x, lp[5:11], ff.fn.norm.eps, prec, drop=d_lay, site=2 + 3 * i)
                 saved += [*s_a, *s_f]
                 consts.append((a.scale, a.heads, dh, attn.fn.norm.eps, ff.fn.norm.eps))
                 i += 1
@@ -705,6 +811,7 @@ class TokenPoseFunction(torch.autograd.Function):
         ctx.geom = (b, c, H, W, ps, nk, n, ntok, dim, prec, m.pos_embedding_type, m.mlp_head[0].eps, depths)
         ctx.aprecs = (aprec, bprec)
         ctx.consts = consts
+        ctx.drops = (d_lay, d_emb)
         ctx.nsaved = len(saved)
         ctx.save_for_backward(*saved, tok, cat, y, *params)
         return out.view(b, nk, m.heatmap_size[0], m.heatmap_size[1])
@@ -729,6 +836,7 @@ class TokenPoseFunction(torch.autograd.Function):
         grads[-4], grads[-3] = layernorm_backward(cat, dy, dcat, params[-4], eps_head, b * nk, 3 * dim)
         del dy
         dcat = dcat.view(b, nk, 3 * dim)
+        d_lay, d_emb = ctx.drops
         per = 9 + 4
         i = sum(depths)
         dx = None
@@ -746,13 +854,15 @@ class TokenPoseFunction(torch.autograd.Function):
                 base = 4 + TP_PER_LAYER * i
                 lp = params[base: base + TP_PER_LAYER]
                 scale, heads, dh, e_a, e_f = ctx.consts[i]
-                grads[base + 5: base + 11] = gelu_ff_backward(dx, sv[9:13], lp[5:11], e_f, prec)
+                grads[base + 5: base + 11] = gelu_ff_backward(dx, sv[9:13], lp[5:11], e_f, prec, drop=d_lay, site=2 + 3 * i)
                 grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_a, scale, heads, dh, 0, ntok, 1, None, None, prec,
-                                                                   bprec=bprec)
+                                                                   bprec=bprec, drop=d_lay, site=1 + 3 * i)
+        if _dropping(d_emb):
+            dropout(dx, d_emb, 0)   # site 0's mask on the token matrix's gradient, before the assembly's gradients
         # token assembly: keypoint_token and the learnable pos_embedding are shared by the batch
-        if ctx.needs_input_grad[5 + 2]:
+        if ctx.needs_input_grad[6 + 2]:
             grads[2] = _joint_sum(dx, nk)
-        if pe_type == "learnable" and ctx.needs_input_grad[5 + 3]:
+        if pe_type == "learnable" and ctx.needs_input_grad[6 + 3]:
             grads[3] = _joint_sum(dx, ntok)
         demb = dx[:, nk:].contiguous().view(b * n, dim)
         need_feat = ctx.needs_input_grad[0]
@@ -761,4 +871,4 @@ class TokenPoseFunction(torch.autograd.Function):
         if need_feat:
             dfeat = torch.empty(b, c, H, W, dtype=torch.float32, device=dev)
             _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dfeat.data_ptr(), b, 1, c, H, W, ps, _st(dout)), "hp_sformer_unpatchify")
-        return (dfeat, None, None, None, None, *grads)
+        return (dfeat, None, None, None, None, None, *grads)

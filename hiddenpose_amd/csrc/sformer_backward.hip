@@ -19,6 +19,7 @@
 #include <cfloat>
 
 #include "hp_internal.h"
+#include "hp_philox.h"
 
 namespace hp {
 
@@ -786,13 +787,44 @@ __global__ __launch_bounds__(SB) void k_attn_bwd_grouped(const float* __restrict
   }
 }
 
+// Phi(t) and phi(t) of the exact erf GELU: what every activation backward below derives from.
+__device__ __forceinline__ void gelu_cdf_pdf(float t, float& cdf, float& pdf) {
+  cdf = 0.5f * (1.0f + erff(t * 0.70710678118654752f));
+  pdf = 0.39894228040143268f * __expf(-0.5f * t * t);
+}
+
 // du = dy * gelu'(u), gelu(u) = u Phi(u): gelu'(u) = Phi(u) + u phi(u) (exact erf form); du may alias dy
 __global__ __launch_bounds__(SB) void k_gelu_bwd(const float* __restrict__ u, const float* dy, float* du, long n) {
   for (long i = (long)blockIdx.x * SB + threadIdx.x; i < n; i += (long)gridDim.x * SB) {
     const float t = u[i];
-    const float cdf = 0.5f * (1.0f + erff(t * 0.70710678118654752f));
-    const float pdf = 0.39894228040143268f * __expf(-0.5f * t * t);
+    float cdf, pdf;
+    gelu_cdf_pdf(t, cdf, pdf);
     du[i] = dy[i] * (cdf + t * pdf);
+  }
+}
+
+// k_gelu_bwd on the dropped gradient: dy first goes through the dropout site's mask (element i of the site's tensor is
+// element i here), g = kept ? dy * scale : 0 rounded once, exactly hp_dropout_forward's value; then the line above.  A thread
+// owns the Philox block's four elements; du may alias dy.
+__global__ __launch_bounds__(SB) void k_gelu_bwd_dropout(const float* __restrict__ u, const float* dy, float* du, long n,
+                                                         const DropoutParams d) {
+  const long ngroups = (n + 3) >> 2;
+  for (long gi = (long)blockIdx.x * SB + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * SB) {
+    const uint4 w4 = philox4x32_10((unsigned long long)gi, d);
+    const unsigned w[4] = {w4.x, w4.y, w4.z, w4.w};
+    float g[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) g[c] = 4 * gi + c < n ? dropout_apply(dy[4 * gi + c], w[c], d) : 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long i = 4 * gi + c;
+      if (i < n) {
+        const float t = u[i];
+        float cdf, pdf;
+        gelu_cdf_pdf(t, cdf, pdf);
+        du[i] = g[c] * (cdf + t * pdf);
+      }
+    }
   }
 }
 
@@ -804,10 +836,53 @@ __global__ __launch_bounds__(SB) void k_geglu_bwd(const float* __restrict__ u, c
     const long r = i / Hd;
     const int c = (int)(i - r * Hd);
     const float a = u[r * 2 * Hd + c], t = u[r * 2 * Hd + Hd + c], g = dg[i];
-    const float cdf = 0.5f * (1.0f + erff(t * 0.70710678118654752f));
-    const float pdf = 0.39894228040143268f * __expf(-0.5f * t * t);
+    float cdf, pdf;
+    gelu_cdf_pdf(t, cdf, pdf);
     du[r * 2 * Hd + c] = g * t * cdf;
     du[r * 2 * Hd + Hd + c] = g * a * (cdf + t * pdf);
+  }
+}
+
+// k_geglu_bwd on the dropped gradient (see k_gelu_bwd_dropout): the site's tensor is dg, (rows, Hd) row-major.  `vec` (the
+// host's finding, uniform): Hd is a multiple of 4 and the three arrays are 16-byte aligned, so a group lies in one row and
+// moves as float4; the arithmetic per element is the same either way.
+__device__ __forceinline__ void geglu_bwd_elem(float a, float t, float g, float& da, float& dt) {
+  float cdf, pdf;
+  gelu_cdf_pdf(t, cdf, pdf);
+  da = g * t * cdf;
+  dt = g * a * (cdf + t * pdf);
+}
+__global__ __launch_bounds__(SB) void k_geglu_bwd_dropout(const float* __restrict__ u, const float* __restrict__ dg,
+                                                          float* __restrict__ du, long rows, int Hd, int vec, const DropoutParams d) {
+  const long total = rows * Hd, ngroups = (total + 3) >> 2;
+  for (long gi = (long)blockIdx.x * SB + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * SB) {
+    const uint4 w4 = philox4x32_10((unsigned long long)gi, d);
+    if (vec) {
+      const long r = (4 * gi) / Hd;
+      const int c = (int)(4 * gi - r * Hd);
+      const float4 g4 = *reinterpret_cast<const float4*>(dg + 4 * gi);
+      const float4 a4 = *reinterpret_cast<const float4*>(u + r * 2 * Hd + c);
+      const float4 t4 = *reinterpret_cast<const float4*>(u + r * 2 * Hd + Hd + c);
+      float4 da, dt;
+      geglu_bwd_elem(a4.x, t4.x, dropout_apply(g4.x, w4.x, d), da.x, dt.x);
+      geglu_bwd_elem(a4.y, t4.y, dropout_apply(g4.y, w4.y, d), da.y, dt.y);
+      geglu_bwd_elem(a4.z, t4.z, dropout_apply(g4.z, w4.z, d), da.z, dt.z);
+      geglu_bwd_elem(a4.w, t4.w, dropout_apply(g4.w, w4.w, d), da.w, dt.w);
+      *reinterpret_cast<float4*>(du + r * 2 * Hd + c) = da;
+      *reinterpret_cast<float4*>(du + r * 2 * Hd + Hd + c) = dt;
+      continue;
+    }
+    const unsigned w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long i = 4 * gi + k;
+      if (i < total) {
+        const long r = i / Hd;
+        const int c = (int)(i - r * Hd);
+        geglu_bwd_elem(u[r * 2 * Hd + c], u[r * 2 * Hd + Hd + c], dropout_apply(dg[i], w[k], d), du[r * 2 * Hd + c],
+                       du[r * 2 * Hd + Hd + c]);
+      }
+    }
   }
 }
 
@@ -1102,6 +1177,35 @@ extern "C" int hp_geglu_backward(const float* u, const float* dg, float* du, lon
   hipStream_t st = (hipStream_t)stream;
   HP_PROF("geglu_bwd", st);
   hipLaunchKernelGGL(k_geglu_bwd, dim3(bgrid(rows * hidden)), dim3(SB), 0, st, u, dg, du, rows, hidden);
+  HP_CHECK_HIP(hipGetLastError());
+  return HP_OK;
+}
+
+extern "C" int hp_geglu_backward_dropout(const float* u, const float* dg, float* du, long rows, int hidden, double p,
+                                         unsigned long long seed, unsigned long long stream, void* stream_handle) {
+  const char* who = "hp_geglu_backward_dropout";
+  HP_REQUIRE(u && dg && du && rows > 0 && hidden > 0, "%s: bad argument (null pointer, rows or hidden <= 0)", who);
+  DropoutParams d;
+  const int rc = dropout_params(who, rows * hidden, 0, p, seed, stream, &d);
+  if (rc != HP_OK) return rc;
+  hipStream_t st = (hipStream_t)stream_handle;
+  HP_PROF("geglu_bwd_dropout", st);
+  const int vec = hidden % 4 == 0 && ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(dg) | reinterpret_cast<uintptr_t>(du)) & 15u) == 0;
+  hipLaunchKernelGGL(k_geglu_bwd_dropout, dim3(bgrid((rows * hidden + 3) / 4)), dim3(SB), 0, st, u, dg, du, rows, hidden, vec, d);
+  HP_CHECK_HIP(hipGetLastError());
+  return HP_OK;
+}
+
+extern "C" int hp_gelu_backward_dropout(const float* u, const float* dy, float* du, long n, double p, unsigned long long seed,
+                                        unsigned long long stream, void* stream_handle) {
+  const char* who = "hp_gelu_backward_dropout";
+  HP_REQUIRE(u && dy && du && n > 0, "%s: bad argument (null pointer or n <= 0)", who);
+  DropoutParams d;
+  const int rc = dropout_params(who, n, 0, p, seed, stream, &d);
+  if (rc != HP_OK) return rc;
+  hipStream_t st = (hipStream_t)stream_handle;
+  HP_PROF("gelu_bwd_dropout", st);
+  hipLaunchKernelGGL(k_gelu_bwd_dropout, dim3(bgrid((n + 3) / 4)), dim3(SB), 0, st, u, dy, du, n, d);
   HP_CHECK_HIP(hipGetLastError());
   return HP_OK;
 }

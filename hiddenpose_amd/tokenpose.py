@@ -11,7 +11,18 @@ _xformer_autograd.TokenPoseFunction (a HIP backward).  `mask` is not supported.
 `attention_precision` / `attention_backward_precision` ("fp32" default, "bf16", "fp16"; NlosPoseSformer's attributes and
 rules) run the all-to-all attention on the 16-bit matrix cores, forward and backward: every token is a patch query here (no
 class queries, one group).  dim // heads must be 32 or 64: the reference's TokenPose-L geometry (8 heads of 24) is refused with
-a 16-bit precision and runs as before otherwise."""
+a 16-bit precision and runs as before otherwise.
+
+Dropout (`dropout` / `emb_dropout`, the reference's keywords) is opt-in by seed, because the HIP path cannot draw from
+torch's global generator: set `dropout_seed` to an int.  It is then ACTIVE while the module is in training mode and one of the
+two probabilities is > 0: every nn.Dropout of the reference's forward is a site whose keep mask is a pure function of
+(dropout_seed, dropout_step, site, element index, p) (Philox4x32-10, hp_dropout_forward), each forward draws its masks and then
+adds 1 to `dropout_step` (also under torch.no_grad(), as torch's dropout follows the training flag alone), setting
+`dropout_step` back replays the same masks, and the backward regenerates them: no mask is stored.  Neither attribute is part
+of the state_dict.  With `dropout_seed` None nothing changes: a training forward with a probability > 0 is refused, the
+no-grad path ignores dropout.  In eval mode nothing is drawn, with or without a seed.  Sites: 0 the token matrix after the position
+embedding (emb_dropout); then per layer, counted through the three stages: the attention's to_out, the hidden activation after
+the GELU, the feed-forward's output (all `dropout`)."""
 from __future__ import annotations
 
 import math
@@ -86,6 +97,8 @@ class TokenPose_L_base(nn.Module):
     # the attention, forward / backward: "fp32" (exact, default), "bf16" or "fp16" (see the module docstring)
     attention_precision = "fp32"
     attention_backward_precision = "fp32"
+    # None: no dropout (training with dropout / emb_dropout > 0 is refused); an int: seeded dropout (module docstring)
+    dropout_seed = None
 
     def __init__(self, *, feature_size, patch_size, num_keypoints, dim, depth, heads, mlp_dim, apply_init=False,
                  hidden_heatmap_dim=64 * 6, heatmap_dim=64 * 48, heatmap_size=(64, 48), channels=3, dropout=0.0, emb_dropout=0.0,
@@ -100,6 +113,7 @@ class TokenPose_L_base(nn.Module):
         self.patch_size, self.heatmap_size, self.num_keypoints = list(patch_size), list(heatmap_size), num_keypoints
         self.pos_embedding_type = pos_embedding_type
         self.dropout, self.emb_dropout = dropout, emb_dropout
+        self.dropout_step = 0   # training forwards drawn so far with dropout active (plain attribute, not in the state_dict)
         self.all_attn = pos_embedding_type == "sine-full"
         self.keypoint_token = nn.Parameter(torch.zeros(1, num_keypoints, dim))
         if pos_embedding_type == "learnable":
@@ -135,20 +149,27 @@ class TokenPose_L_base(nn.Module):
     def forward(self, feature, mask=None):
         """An autograd graph (_xformer_autograd.TokenPoseFunction) is built when grad mode is on, the module is in training
         mode or `feature` requires grad, and something (a parameter or `feature`) requires grad.  Its forward runs the same
-        kernels in the same order as the no-graph path (the output is bit-identical); training needs dropout 0.  Otherwise
-        the no-graph path runs, launch for launch as an inference-only module would."""
+        kernels in the same order as the no-graph path (the output is bit-identical while dropout is not active); training with
+        a dropout probability > 0 needs dropout_seed (module docstring).  Otherwise the no-graph path runs, launch for launch
+        as an inference-only module would.  With dropout active the forward always goes through TokenPoseFunction, under
+        no_grad too, and adds 1 to dropout_step."""
         assert mask is None, "masks are not supported"
         if not feature.is_cuda:
             raise _lib.HiddenPoseHipError("TokenPose.forward needs a tensor on a HIP device; there is no CPU path")
         params = _xa.tokenpose_params(self)
-        if (torch.is_grad_enabled() and (self.training or feature.requires_grad)
-                and (feature.requires_grad or any(p.requires_grad for p in params))):
-            if self.dropout > 0 or self.emb_dropout > 0:
-                raise _lib.HiddenPoseHipError("TokenPose training: dropout is not built (dropout / emb_dropout must be 0)")
+        drop = _xa.active_dropout(self, self.dropout, self.emb_dropout)
+        if drop is not None or (torch.is_grad_enabled() and (self.training or feature.requires_grad)
+                                and (feature.requires_grad or any(p.requires_grad for p in params))):
+            if drop is None and (self.dropout_seed is None or self.training) and (self.dropout > 0 or self.emb_dropout > 0):
+                raise _lib.HiddenPoseHipError("TokenPose training: dropout is not built without a seed (dropout / emb_dropout must "
+                                              "be 0; set dropout_seed to enable)")
             aprec, bprec = X.attention_precisions(self, self.dim_head, training=True)
             with torch.cuda.device(feature.device):
-                return _xa.TokenPoseFunction.apply(feature.contiguous().float(), self, X.PREC[self.linear_precision], aprec, bprec,
-                                                   *params)
+                out = _xa.TokenPoseFunction.apply(feature.contiguous().float(), self, X.PREC[self.linear_precision], aprec, bprec,
+                                                  drop, *params)
+            if drop is not None:
+                self.dropout_step += 1
+            return out
         with torch.no_grad():
             return self._forward_nograd(feature)
 

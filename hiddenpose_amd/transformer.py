@@ -21,7 +21,18 @@ rules: dim_head 32 or 64, a 16-bit forward needs a 16-bit backward, a 16-bit bac
 attention's patch queries on the 16-bit matrix cores, forward and backward, with and without `mask`: n patches per frame
 attend to [class | their frame], which is where the attention's work is.  The time attention stays exact fp32 (its groups
 have f + 1 keys: a 32-key MFMA tile would be mostly padding, and its backward is the grouped fp32 kernel), and so do the class
-queries in both attentions (one query over every token, the only query that applies the spatial mask)."""
+queries in both attentions (one query over every token, the only query that applies the spatial mask).
+
+Dropout (`attn_dropout` / `ff_dropout`, the reference's keywords) is opt-in by seed, because the HIP path cannot draw from
+torch's global generator: set `dropout_seed` to an int.  It is then ACTIVE while the module is in training mode and one of the
+two probabilities is > 0: every nn.Dropout of the reference's forward is a site whose keep mask is a pure function of
+(dropout_seed, dropout_step, site, element index, p) (Philox4x32-10, hp_dropout_forward), each forward draws its masks and then
+adds 1 to `dropout_step` (also under torch.no_grad(), as torch's dropout follows the training flag alone), setting
+`dropout_step` back replays the same masks, and the backward regenerates them: no mask is stored.  Neither attribute is part
+of the state_dict.  With `dropout_seed` None nothing changes: a training forward with a probability > 0 is refused, the
+no-grad path ignores dropout.  In eval mode nothing is drawn, with or without a seed.  Sites per layer: the time attention's
+to_out (on the un-permuted rows, as in the reference), the spatial attention's to_out (both attn_dropout), the feed-forward's
+hidden activation after the GEGLU (ff_dropout)."""
 from __future__ import annotations
 
 from math import log, pi
@@ -64,6 +75,8 @@ class TimeSformer(nn.Module):
     # the spatial attention's patch queries, forward / backward: "fp32" (exact, default), "bf16" or "fp16" (see the module docstring)
     attention_precision = "fp32"
     attention_backward_precision = "fp32"
+    # None: no dropout (training with attn_dropout / ff_dropout > 0 is refused); an int: seeded dropout (module docstring)
+    dropout_seed = None
 
     def __init__(self, *, dim, num_frames, num_classes=None, image_size=224, patch_size=16, channels=3, depth=12, heads=8,
                  dim_head=64, attn_dropout=0.0, ff_dropout=0.0, rotary_emb=True, shift_tokens=False):
@@ -73,6 +86,7 @@ class TimeSformer(nn.Module):
         _lib.lib()
         self.heads, self.dim_head, self.patch_size, self.num_frames, self.shift_tokens = heads, dim_head, patch_size, num_frames, shift_tokens
         self.attn_dropout, self.ff_dropout = attn_dropout, ff_dropout
+        self.dropout_step = 0   # training forwards drawn so far with dropout active (plain attribute, not in the state_dict)
         self.to_patch_embedding = nn.Linear(channels * patch_size ** 2, dim)
         self.cls_token = nn.Parameter(torch.randn(1, dim))
         self.frame_rot_emb = RotaryEmbedding(dim_head)
@@ -108,8 +122,10 @@ class TimeSformer(nn.Module):
         else raises ValueError.
         An autograd graph (_xformer_autograd.TimeSformerFunction) is built when grad mode is on, the module is in
         training mode or `video` requires grad, and something (a parameter or `video`) requires grad.  Its forward runs the
-        same kernels in the same order as the no-graph path (the output is bit-identical); training needs dropout 0.
-        Otherwise the no-graph path runs, launch for launch as an inference-only module would."""
+        same kernels in the same order as the no-graph path (the output is bit-identical while dropout is not active); training
+        with a dropout probability > 0 needs dropout_seed (module docstring).  Otherwise the no-graph path runs, launch for
+        launch as an inference-only module would.  With dropout active the forward always goes through
+        TimeSformerFunction, under no_grad too, and adds 1 to dropout_step."""
         if not video.is_cuda:
             raise _lib.HiddenPoseHipError("TimeSformer.forward needs a tensor on a HIP device; there is no CPU path")
         masks = (None, None)
@@ -117,14 +133,19 @@ class TimeSformer(nn.Module):
             ps = self.patch_size
             masks = self._key_masks(mask, video, (video.shape[-2] // ps) * (video.shape[-1] // ps))
         params = _xa.timesformer_params(self)
-        if (torch.is_grad_enabled() and (self.training or video.requires_grad)
-                and (video.requires_grad or any(p.requires_grad for p in params))):
-            if self.attn_dropout > 0 or self.ff_dropout > 0:
-                raise _lib.HiddenPoseHipError("TimeSformer training: dropout is not built (attn_dropout / ff_dropout must be 0)")
+        drop = _xa.active_dropout(self, self.attn_dropout, self.ff_dropout)
+        if drop is not None or (torch.is_grad_enabled() and (self.training or video.requires_grad)
+                                and (video.requires_grad or any(p.requires_grad for p in params))):
+            if drop is None and (self.dropout_seed is None or self.training) and (self.attn_dropout > 0 or self.ff_dropout > 0):
+                raise _lib.HiddenPoseHipError("TimeSformer training: dropout is not built without a seed (attn_dropout / ff_dropout "
+                                              "must be 0; set dropout_seed to enable)")
             aprec, bprec = X.attention_precisions(self, self.dim_head, training=True)
             with torch.cuda.device(video.device):
-                return _xa.TimeSformerFunction.apply(video.contiguous().float(), self, X.PREC[self.linear_precision], aprec, bprec,
-                                                     *masks, *params)
+                out = _xa.TimeSformerFunction.apply(video.contiguous().float(), self, X.PREC[self.linear_precision], aprec, bprec,
+                                                    *masks, drop, *params)
+            if drop is not None:
+                self.dropout_step += 1
+            return out
         with torch.no_grad():
             return self._forward_nograd(video, *masks)
 

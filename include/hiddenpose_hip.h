@@ -611,6 +611,26 @@ int hp_geglu_backward(const float* u, const float* dg, float* du, long rows, int
 /* GELU backward (nn.GELU(), exact erf form, the derivative of hp_gelu_forward): du = dy * gelu'(u) over n values; du may
  * alias dy. */
 int hp_gelu_backward(const float* u, const float* dy, float* du, long n, void* stream);
+/* Seeded dropout of the transformer heads' training paths.  The mask is a pure function of
+ * (seed, stream, e, p): element e of a tensor's flat row-major index space takes output word e & 3 of the Philox4x32-10
+ * block with counter (lo32(e >> 2), hi32(e >> 2), lo32(stream), hi32(stream)) and key (lo32(seed), hi32(seed)) and is
+ * kept iff word >= floor(p 2^32 + 0.5); kept values are multiplied by (float)(1 / (1 - p)) (0 when p = 1).  p in [0, 1].
+ *
+ * y[i] = (kept(first + i) ? x[i] * scale : 0) [+ addend[i]];  addend may be NULL; y may be x or addend itself (no other
+ * overlap).  Two roundings when addend is given: the product, then the sum.  `first`: flat index of x[0] in the logical
+ * tensor (a caller may process a tensor in slices).  The backward of a site is the same entry with addend NULL.  n == 0
+ * returns HP_OK; every refusal comes before any device call. */
+int hp_dropout_forward(const float* x, const float* addend, float* y, long n, long first, double p, unsigned long long seed,
+                       unsigned long long stream, void* stream_handle);
+/* mask[i] = kept(first + i) ? 1 : 0 -- for tests and debugging */
+int hp_dropout_mask(unsigned char* mask, long n, long first, double p, unsigned long long seed, unsigned long long stream,
+                    void* stream_handle);
+/* hp_geglu_backward / hp_gelu_backward on a gradient that first goes through a dropout site's mask (the site's tensor is dg
+ * (rows, hidden) / dy (n)): bit-identical to hp_dropout_forward(dg) followed by the plain entry, without the extra pass. */
+int hp_geglu_backward_dropout(const float* u, const float* dg, float* du, long rows, int hidden, double p,
+                              unsigned long long seed, unsigned long long stream, void* stream_handle);
+int hp_gelu_backward_dropout(const float* u, const float* dy, float* du, long n, double p, unsigned long long seed,
+                             unsigned long long stream, void* stream_handle);
 /* nn.Linear data gradient dx (M, K) = dy (M, N) @ w (N, K) [+ addend] (addend may be NULL, must not be dx): the 1x1x1
  * convolution data gradient with its packed weight image built into the workspace.  precision as the forward's. */
 size_t hp_linear_backward_data_workspace_bytes(int K, int N);

@@ -6,7 +6,10 @@ time in fp32 (from the step) and with fp16 patch attention (a no-graph forward o
 
     python tools/time_sformer_train.py [--batch 8] [--steps 5] [--warmup 2] [--heads 8] [--dim-head 32]
                                        [--attention fp32|bf16|fp16] [--attention-backward fp32|bf16|fp16] [--linear fp32|bf16]
+                                       [--dropout P] [--ab-rounds 5]
 
+--dropout P sets attn_dropout = ff_dropout = P and a dropout_seed (seeded Philox dropout): every figure is then
+taken with dropout active, and "dropout_ab" adds the step with dropout 0 against dropout P in alternating rounds.
 --attention / --attention-backward are NlosPoseSformer.attention_precision / attention_backward_precision (a 16-bit forward
 needs a 16-bit backward to train).  The attention backward's time is reported on the same five-product FLOP count at every
 precision, as a fraction of the fp32 MFMA peak, of the 2.5 PF/s bf16 MFMA peak, and as exponentials per second (two per score:
@@ -46,9 +49,28 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) * 1e3 / steps
 
 
+def dropout_ab(step, set_dropout, p, rounds, steps):
+    """The training step with dropout 0 against dropout p: same process, alternating rounds of `steps` timed steps each.
+    -> per-round times, medians, the overhead and the spread (max - min) of the dropout-0 leg."""
+    off, on = [], []
+    for _ in range(rounds):
+        set_dropout(0.0)
+        step()
+        off.append(timed(step, steps))
+        set_dropout(p)
+        step()
+        on.append(timed(step, steps))
+    med = lambda v: sorted(v)[len(v) // 2]
+    return {"p": p, "rounds": rounds, "steps_per_round": steps, "off_ms": [round(t, 2) for t in off], "on_ms": [round(t, 2) for t in on],
+            "median_off_ms": round(med(off), 2), "median_on_ms": round(med(on), 2), "overhead_ms": round(med(on) - med(off), 2),
+            "off_spread_ms": round(max(off) - min(off), 2), "on_spread_ms": round(max(on) - min(on), 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--dropout", type=float, default=0.0, help="attn_dropout = ff_dropout = P, with a dropout_seed")
+    ap.add_argument("--ab-rounds", type=int, default=5, help="alternating rounds of the dropout 0 / P comparison")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--heads", type=int, default=8)
@@ -65,6 +87,12 @@ def main():
     hpt.fill_module(m, "sformer.")
     m = m.cuda()
     m.attention_precision, m.attention_backward_precision, m.linear_precision = a.attention, a.attention_backward, a.linear
+
+    def set_dropout(p):
+        m.attn_dropout = m.ff_dropout = p
+        m.dropout_seed = 1234 if p > 0 else None
+
+    set_dropout(a.dropout)
     B = a.batch
     video = torch.rand(B, 16, 1, 128, 128, generator=torch.Generator().manual_seed(5)).cuda()
     R = torch.randn(B, 24, 4, 128, generator=torch.Generator().manual_seed(6)).cuda()
@@ -101,6 +129,7 @@ def main():
     torch.cuda.synchronize()
     prof = _lib.profile_read()
     _lib.profile_enable(False)
+    ab = dropout_ab(step, set_dropout, a.dropout, a.ab_rounds, a.steps) if a.dropout > 0 else None
     attn_fwd = lambda pr: sum(ms for k, (_, ms) in pr.items() if k.startswith("sformer_attention_"))
     attn_fwd_ms = attn_fwd(prof)
     # the same forward with the fp16 patch attention: a no-graph forward, profiled on its own
@@ -123,7 +152,7 @@ def main():
     exps = depth * 2 * (B * heads * f * n * (nj + n) + B * heads * nj * ntok)
     print(json.dumps({
         "config": "config5", "batch": B, "precision": a.linear, "attention": a.attention, "attention_backward": a.attention_backward,
-        "heads": a.heads, "dim_head": a.dim_head,
+        "heads": a.heads, "dim_head": a.dim_head, "dropout": a.dropout, "dropout_ab": ab,
         "forward_nograd_ms": round(t_nograd, 2), "forward_graph_ms": round(t_graph, 2),
         "backward_ms": round(t_step - t_graph, 2), "step_ms": round(t_step, 2), "step_over_nograd_forward": round(t_step / t_nograd, 2),
         "attention_forward_ms": round(attn_fwd_ms, 2), "attention_forward_fp16_ms": round(attn_fwd_fp16_ms, 2),

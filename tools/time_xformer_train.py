@@ -8,7 +8,11 @@ inputs, same process, median of the timed calls); the device's maxGridSize; and 
     python tools/time_xformer_train.py [--steps 5] [--warmup 2] [--ab-calls 20] [--heads 8] [--dim-head 32]
                                        [--valid-frames K] [--timesformer-only]
                                        [--attention fp32|bf16|fp16] [--attention-backward fp32|bf16|fp16] [--linear fp32|bf16]
+                                       [--dropout P] [--ab-rounds 5]
 
+--dropout P sets every dropout probability of both heads to P and a dropout_seed (seeded Philox dropout): the
+heads' figures are then taken with dropout active, and each head's "dropout_ab" adds the step with dropout 0 against dropout
+P in alternating rounds.
 --heads / --dim-head set TimeSformer's head split (dim stays 256).  TokenPose-L keeps dim 192 and its 8 heads of 24 unless
 --dim-head is given: then it runs 192 // dim_head heads (3 heads of 64).  The grouped time-attention backward is not built
 for dim_head 64; the A/B is skipped there and the step takes the generic entry.
@@ -58,9 +62,34 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) * 1e3 / steps
 
 
-def head_timing(m, x, R, steps, warmup, **fkw):
-    """fkw: extra keyword arguments of the module's forward (TimeSformer's mask)."""
+def dropout_ab(step, set_dropout, p, rounds, steps):
+    """The training step with dropout 0 against dropout p: same process, alternating rounds of `steps` timed steps each.
+    -> per-round times, medians, the overhead and the spread (max - min) of the dropout-0 leg."""
+    off, on = [], []
+    for _ in range(rounds):
+        set_dropout(0.0)
+        step()
+        off.append(timed(step, steps))
+        set_dropout(p)
+        step()
+        on.append(timed(step, steps))
+    med = lambda v: sorted(v)[len(v) // 2]
+    return {"p": p, "rounds": rounds, "steps_per_round": steps, "off_ms": [round(t, 2) for t in off], "on_ms": [round(t, 2) for t in on],
+            "median_off_ms": round(med(off), 2), "median_on_ms": round(med(on), 2), "overhead_ms": round(med(on) - med(off), 2),
+            "off_spread_ms": round(max(off) - min(off), 2), "on_spread_ms": round(max(on) - min(on), 2)}
+
+
+def head_timing(m, x, R, steps, warmup, dropout=0.0, ab_rounds=5, **fkw):
+    """fkw: extra keyword arguments of the module's forward (TimeSformer's mask).  dropout: every probability of the module."""
     m = m.cuda()
+
+    def set_dropout(p):
+        for attr in ("attn_dropout", "ff_dropout", "dropout", "emb_dropout"):
+            if hasattr(m, attr):
+                setattr(m, attr, p)
+        m.dropout_seed = 1234 if p > 0 else None
+
+    set_dropout(dropout)
 
     def fwd_nograd():
         with torch.no_grad():
@@ -94,6 +123,7 @@ def head_timing(m, x, R, steps, warmup, **fkw):
     prof = _lib.profile_read()
     _lib.profile_enable(False)
     return {
+        "dropout": dropout, "dropout_ab": dropout_ab(step, set_dropout, dropout, ab_rounds, steps) if dropout > 0 else None,
         "forward_nograd_ms": round(t_nograd, 2), "forward_graph_ms": round(t_graph, 2), "backward_ms": round(t_step - t_graph, 2),
         "step_ms": round(t_step, 2), "step_over_nograd_forward": round(t_step / t_nograd, 2), "peak_memory_gb": round(peak / 1e9, 2),
         "kernels_ms": {k: [cnt, round(ms, 3)] for k, (cnt, ms) in sorted(prof.items(), key=lambda kv: -kv[1][1])},
@@ -171,6 +201,8 @@ def main():
     ap.add_argument("--attention", choices=("fp32", "bf16", "fp16"), default="fp32")
     ap.add_argument("--attention-backward", choices=("fp32", "bf16", "fp16"), default="fp32")
     ap.add_argument("--linear", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--dropout", type=float, default=0.0, help="every dropout probability of both heads, with a dropout_seed")
+    ap.add_argument("--ab-rounds", type=int, default=5, help="alternating rounds of the dropout 0 / P comparison")
     a = ap.parse_args()
     if a.attention != "fp32" and a.attention_backward == "fp32":
         ap.error("--attention bf16 / fp16 needs --attention-backward bf16 / fp16 (the 16-bit patch attention has no fp32 backward)")
@@ -196,7 +228,7 @@ def main():
     if a.valid_frames is not None:
         assert 0 <= a.valid_frames <= TS_KW["num_frames"], "--valid-frames must lie in 0 .. 16"
         fkw["mask"] = (torch.arange(TS_KW["num_frames"]) < a.valid_frames)[None].expand(4, -1).contiguous().cuda()
-    out["timesformer"] = {"batch": 4, "depth": 8, "valid_frames": a.valid_frames, **head_timing(ts, video, R, a.steps, a.warmup, **fkw)}
+    out["timesformer"] = {"batch": 4, "depth": 8, "valid_frames": a.valid_frames, **head_timing(ts, video, R, a.steps, a.warmup, a.dropout, a.ab_rounds, **fkw)}
     del video, R
     torch.cuda.empty_cache()
     if a.timesformer_only:
@@ -207,7 +239,7 @@ def main():
     tp.attention_precision, tp.attention_backward_precision, tp.linear_precision = a.attention, a.attention_backward, a.linear
     feat = torch.rand(8, 128, 64, 64, generator=torch.Generator().manual_seed(5)).cuda()
     R = torch.randn(8, 16, 64, 64, generator=torch.Generator().manual_seed(6)).cuda()
-    out["tokenpose_l"] = {"batch": 8, **head_timing(tp, feat, R, a.steps, a.warmup)}
+    out["tokenpose_l"] = {"batch": 8, **head_timing(tp, feat, R, a.steps, a.warmup, a.dropout, a.ab_rounds)}
     del tp, feat, R
     torch.cuda.empty_cache()
     out["timesformer_forward_batch8"] = forward_batch8_launches(ts)   # last: a refused launch ends nothing else
