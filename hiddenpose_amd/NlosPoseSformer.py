@@ -18,7 +18,6 @@ to_out (attn_dropout), then the feed-forward's hidden activation after the GEGLU
 """
 from __future__ import annotations
 
-import ctypes as C
 from math import log, pi
 
 import torch
@@ -74,20 +73,6 @@ class _FeedForward(nn.Module):
         self.net = nn.Sequential(nn.Linear(dim, dim * mult * 2), nn.Identity(), nn.Identity(), nn.Linear(dim * mult, dim))
 
 
-_LINEAR_PRECISION = {"fp32": 0, "bf16": 1, "bf16x3": 2, "bf16x6": 3}  # HP_PRECISION_*
-_ATTENTION_PRECISION = {"fp32": 0, "bf16": 1, "fp16": 4}
-
-
-def _linear(x2d, weight, bias, precision=0, residual=None):
-    """y = x @ W^T + b (+ residual, written in place into `residual`) through hp_linear_forward.  x2d (M, K) contiguous."""
-    M, K = x2d.shape
-    N = weight.shape[0]
-    y = residual if residual is not None else torch.empty(M, N, dtype=torch.float32, device=x2d.device)
-    _lib.check(_lib.lib().hp_linear_forward(x2d.data_ptr(), weight.data_ptr(), _lib.ptr(bias), _lib.ptr(residual), y.data_ptr(),
-                                            M, K, N, precision, _lib.current_stream_handle(x2d.device)), "hp_linear_forward")
-    return y
-
-
 class NlosPoseSformer(nn.Module):
     # arithmetic of the transformer-layer Linear GEMMs: "fp32" (exact, default) or the bf16 matrix-core modes of
     # hp_conv_desc.precision; attention, LayerNorm, GEGLU, patch embedding and the output head stay fp32
@@ -132,22 +117,13 @@ class NlosPoseSformer(nn.Module):
         if not video.is_cuda:
             raise _lib.HiddenPoseHipError("NlosPoseSformer.forward needs a tensor on a HIP device; there is no CPU path")
         params = _xa.trainable_params(self)
-        drop = _xa.active_dropout(self, self.attn_dropout, self.ff_dropout)
-        if drop is not None or (torch.is_grad_enabled() and (self.training or video.requires_grad)
-                                and (video.requires_grad or any(p.requires_grad for p in params))):
-            if drop is None and (self.dropout_seed is None or self.training) and (self.attn_dropout > 0 or self.ff_dropout > 0):
-                raise _lib.HiddenPoseHipError("NlosPoseSformer training: dropout is not built without a seed (attn_dropout / "
-                                              "ff_dropout must be 0; set dropout_seed to enable)")
-            aprec = {"fp32": 0, "bf16": 1, "fp16": 4}[self.attention_precision]
-            if self.attention_backward_precision not in _ATTENTION_PRECISION:
-                raise _lib.HiddenPoseHipError(f"attention_backward_precision {self.attention_backward_precision!r}: one of "
-                                              "\"fp32\", \"bf16\", \"fp16\"")
-            bprec = _ATTENTION_PRECISION[self.attention_backward_precision]
-            if (aprec or bprec) and self.dim_head not in (32, 64):
-                raise _lib.HiddenPoseHipError("bf16 / fp16 attention is built for dim_head 32 and 64 only")
+        graph, drop = _xa.training_gate(self, video, params, self.attn_dropout, self.ff_dropout, "NlosPoseSformer", "attn_dropout",
+                                        "ff_dropout")
+        if graph:
+            aprec, bprec = _xf.attention_precisions(self, self.dim_head, training=True)
             with torch.cuda.device(video.device):
-                out = _xa.SformerFunction.apply(video.contiguous().float(), self, _LINEAR_PRECISION[self.linear_precision], aprec,
-                                                bprec, drop, *params)
+                out = _xa.SformerFunction.apply(video.contiguous().float(), self, _xf.PREC[self.linear_precision], aprec, bprec, drop,
+                                                *params)
             if drop is not None:
                 self.dropout_step += 1
             return out
@@ -161,21 +137,13 @@ class NlosPoseSformer(nn.Module):
         ps, nj, heads, dh = self.patch_size, self.num_joints, self.heads, self.dim_head
         hp, wp = H // ps, W // ps
         n = hp * wp
-        ntok = nj + f * n
-        dim = self.joints_token.shape[-1]
         dev = video.device
         st = _lib.current_stream_handle(dev)
-        prec = _LINEAR_PRECISION[self.linear_precision]
-        aprec = {"fp32": 0, "bf16": 1, "fp16": 4}[self.attention_precision]
-        if aprec and dh not in (32, 64):
-            raise _lib.HiddenPoseHipError("bf16 / fp16 attention is built for dim_head 32 and 64 only")
+        prec = _xf.PREC[self.linear_precision]
+        aprec, _ = _xf.attention_precisions(self, dh, training=False)
         with torch.cuda.device(dev):
-            tokens = torch.empty(b * f * n, ps * ps * c, dtype=torch.float32, device=dev)
-            _lib.check(L.hp_sformer_patchify(video.data_ptr(), tokens.data_ptr(), b, f, c, H, W, ps, st), "hp_sformer_patchify")
-            emb = _linear(tokens, self.to_patch_embedding.weight, self.to_patch_embedding.bias)
-            x = torch.empty(b, ntok, dim, dtype=torch.float32, device=dev)
-            x[:, :nj] = self.joints_token          # token-matrix assembly: plain copies
-            x[:, nj:] = emb.view(b, f * n, dim)
+            _, x = _xf.embed_tokens(video, ps, self.to_patch_embedding.weight, self.to_patch_embedding.bias, self.joints_token)
+            ntok, dim = x.shape[1:]
             sin_t, cos_t = self.image_rot_emb.tables(hp, wp, dev)
             rot_dim = sin_t.shape[-1]
             rows = b * ntok
@@ -186,24 +154,21 @@ class NlosPoseSformer(nn.Module):
             k0 = torch.empty_like(q)
             v = torch.empty_like(q)
             att = torch.empty(b, ntok, inner, dtype=torch.float32, device=dev)
-            aws = torch.empty(int(L.hp_sformer_attention_workspace_bytes(b, heads, dh)) // 4, dtype=torch.float32, device=dev)
+            aws = _xf.attention_workspace(b, heads, dh, dev)
             for _time_attn, spatial, ff in self.layers:
                 a = spatial.fn
                 _lib.check(L.hp_layernorm_forward(x.data_ptr(), h.data_ptr(), rows, dim, spatial.norm.weight.data_ptr(),
                                                   spatial.norm.bias.data_ptr(), spatial.norm.eps, 0, 0, st), "hp_layernorm_forward")
-                qkv = _linear(h.view(rows, dim), a.to_qkv.weight, None, prec)
+                qkv = _xf.linear(h.view(rows, dim), a.to_qkv.weight, None, prec)
                 _lib.check(L.hp_sformer_qkv_prepare(qkv.data_ptr(), q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), b, ntok, heads, dh,
                                                     nj, n, a.scale, sin_t.data_ptr(), cos_t.data_ptr(), rot_dim, st),
                            "hp_sformer_qkv_prepare")
-                _lib.check(L.hp_sformer_attention(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh, ntok, nj,
-                                                  n, f, aprec, aws.data_ptr(), st), "hp_sformer_attention")
-                _linear(att.view(rows, inner), a.to_out[0].weight, a.to_out[0].bias, prec, residual=x.view(rows, dim))
+                _xf.attention_forward(q, k, k0, v, att, None, b, heads, dh, ntok, nj, n, f, aws, precision=aprec)
+                _xf.linear(att.view(rows, inner), a.to_out[0].weight, a.to_out[0].bias, prec, residual=x.view(rows, dim))
                 _lib.check(L.hp_layernorm_forward(x.data_ptr(), h.data_ptr(), rows, dim, ff.norm.weight.data_ptr(),
                                                   ff.norm.bias.data_ptr(), ff.norm.eps, 0, 0, st), "hp_layernorm_forward")
                 # feed-forward: Linear -> GEGLU (in the GEMM's epilogue) -> Linear + residual
                 _xf.geglu_ff(x.view(rows, dim), h.view(rows, dim), ff.fn.net[0], ff.fn.net[3], prec)
-            jt = torch.empty(b * nj, dim, dtype=torch.float32, device=dev)
-            _lib.check(L.hp_layernorm_forward(x.data_ptr(), jt.data_ptr(), b * nj, dim, self.to_out[0].weight.data_ptr(),
-                                              self.to_out[0].bias.data_ptr(), self.to_out[0].eps, nj, ntok, st), "hp_layernorm_forward")
-            out = _linear(jt, self.to_out[1].weight, self.to_out[1].bias)
+            jt = _xf.layernorm(x, self.to_out[0], rows=b * nj, rows_per_batch=nj, batch_stride_rows=ntok)
+            out = _xf.linear(jt, self.to_out[1].weight, self.to_out[1].bias)
         return out.view(b, nj, 4, -1)

@@ -1,12 +1,14 @@
 """Building blocks shared by the transformer heads (transformer.TimeSformer, tokenpose.TokenPose_L_base): every
 arithmetic step is a kernel of libhiddenpose_hip.so (Linear = the MFMA GEMM, LayerNorm, qkv split + rotary,
 flash-style attention, GEGLU / GELU); PyTorch only owns the buffers.  These are the no-graph (inference) forms; the
-training paths of the heads are in _xformer_autograd.py."""
+training paths of the heads are in _xformer_autograd.py, which shares attention_forward, embed_tokens, add_position_embedding
+and time_perm / time_unperm with them."""
 from __future__ import annotations
 
 import torch
 
 from . import _lib
+from . import hip_ops as ops
 
 PREC = {"fp32": 0, "bf16": 1, "bf16x3": 2, "bf16x6": 3}
 ATTENTION_PREC = {"fp32": 0, "bf16": 1, "fp16": 4}   # HP_PRECISION_* of the attention's patch queries
@@ -14,8 +16,8 @@ ATTENTION_PREC = {"fp32": 0, "bf16": 1, "fp16": 4}   # HP_PRECISION_* of the att
 
 def attention_precisions(module, dim_head, training):
     """HP_PRECISION_* codes of module.attention_precision and (training only, else 0) module.attention_backward_precision,
-    with NlosPoseSformer's rules: a name outside fp32 / bf16 / fp16 and a 16-bit precision at a dim_head other than 32 / 64
-    raise HiddenPoseHipError."""
+    with the rules of all three heads: a name outside fp32 / bf16 / fp16 and a 16-bit precision at a dim_head other than
+    32 / 64 raise HiddenPoseHipError."""
     names = ("attention_precision", "attention_backward_precision") if training else ("attention_precision",)
     codes = []
     for name in names:
@@ -57,9 +59,9 @@ def attention(h2d, to_qkv, b, ntok, heads, dh, nj, n, frames, scale, sin_t=None,
     to every token (keys without rotary embedding), a group's tokens to [class tokens | their group] with the rotary
     tables (n, rot_dim) applied to q and k.  h2d: (b * ntok, dim) normalised input -> (b, ntok, heads * dh).
     key_mask: None (today's call, launch for launch) or a (b, ntok) uint8 tensor in this call's token order, nonzero =
-    attendable (hp_sformer_attention_masked_p): the class queries leave the masked tokens out, the group queries too when
-    mask_patch_queries.  attention_precision: HP_PRECISION_* of the group (patch) queries, 0 / 1 (bf16) / 4 (fp16); the 16-bit
-    kernels need dh 32 or 64 and, with a key_mask, mask_patch_queries False.  The class queries are always exact fp32."""
+    attendable: the class queries leave the masked tokens out, the group queries too when mask_patch_queries.
+    attention_precision: HP_PRECISION_* of the group (patch) queries, 0 / 1 (bf16) / 4 (fp16); the 16-bit kernels need dh 32
+    or 64 and, with a key_mask, mask_patch_queries False.  The class queries are always exact fp32."""
     L = _lib.lib()
     dev = h2d.device
     inner = heads * dh
@@ -70,16 +72,38 @@ def attention(h2d, to_qkv, b, ntok, heads, dh, nj, n, frames, scale, sin_t=None,
     _lib.check(L.hp_sformer_qkv_prepare(qkv.data_ptr(), q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), b, ntok, heads, dh, nj,
                                         n, scale, _lib.ptr(sin_t), _lib.ptr(cos_t), rot_dim, _st(h2d)), "hp_sformer_qkv_prepare")
     att = torch.empty(b, ntok, inner, dtype=torch.float32, device=dev)
-    ws = torch.empty(max(1, int(L.hp_sformer_attention_workspace_bytes(b, heads, dh)) // 4), dtype=torch.float32, device=dev)
-    if key_mask is None:
-        _lib.check(L.hp_sformer_attention(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh, ntok, nj, n,
-                                          frames, attention_precision, ws.data_ptr(), _st(h2d)), "hp_sformer_attention")
-    else:
+    if key_mask is not None:
         check_key_mask(key_mask, b, ntok, dev)
-        _lib.check(L.hp_sformer_attention_masked_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh,
-                                                   ntok, nj, n, frames, key_mask.data_ptr(), int(bool(mask_patch_queries)),
-                                                   attention_precision, ws.data_ptr(), _st(h2d)), "hp_sformer_attention_masked_p")
+    attention_forward(q, k, k0, v, att, None, b, heads, dh, ntok, nj, n, frames, attention_workspace(b, heads, dh, dev), key_mask,
+                      mask_patch_queries, attention_precision)
     return att
+
+
+def attention_workspace(b, heads, dh, dev):
+    nbytes = int(_lib.lib().hp_sformer_attention_workspace_bytes(b, heads, dh))
+    return torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=dev)
+
+
+def attention_forward(q, k, k0, v, att, lse, b, heads, dh, ntok, nj, n, groups, ws, key_mask=None, mask_patch_queries=False,
+                      precision=0):
+    """The attention of q, k, k0, v (b, heads, ntok, dh) over [nj | groups x n] into att (b, ntok, heads * dh) and, unless
+    None, the soft-max's log-sum-exp into lse (b, heads, ntok): the one place that chooses among the forward entries.  ws:
+    attention_workspace(b, heads, dh, device).  Without lse the precision (HP_PRECISION_* of the patch queries) is an argument
+    of the entry; with lse the fp32 and the 16-bit kernels have entries of their own."""
+    L = _lib.lib()
+    mask = () if key_mask is None else (key_mask.data_ptr(), int(bool(mask_patch_queries)))
+    if lse is None:
+        entry = L.hp_sformer_attention if key_mask is None else L.hp_sformer_attention_masked_p
+        tail = (*mask, precision)
+    elif precision == 0:
+        entry = L.hp_sformer_attention_lse if key_mask is None else L.hp_sformer_attention_lse_masked
+        tail = mask
+    else:
+        entry = L.hp_sformer_attention_lse_p if key_mask is None else L.hp_sformer_attention_lse_masked_p
+        tail = (*mask, precision)
+    out = (att.data_ptr(),) if lse is None else (att.data_ptr(), lse.data_ptr())
+    _lib.check(entry(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), *out, b, heads, dh, ntok, nj, n, groups, *tail,
+                     ws.data_ptr(), _st(q)), entry.__name__)
 
 
 def check_key_mask(key_mask, b, ntok, dev):
@@ -119,3 +143,45 @@ def patchify(video, patch):
     tokens = torch.empty(b * f * (H // patch) * (W // patch), patch * patch * c, dtype=torch.float32, device=video.device)
     _lib.check(_lib.lib().hp_sformer_patchify(video.data_ptr(), tokens.data_ptr(), b, f, c, H, W, patch, _st(video)), "hp_sformer_patchify")
     return tokens
+
+
+def embed_tokens(video, patch, weight, bias, lead):
+    """video (b, f, c, H, W) -> (tokens, x): the patch rows (b f h w, p1 p2 c) and the token matrix [lead | Linear(tokens)]
+    (b, nl + f h w, dim), lead (1, nl, dim) or (nl, dim) being the leading (class / joint / keypoint) tokens every sample
+    shares.  The assembly is plain copies."""
+    b = video.shape[0]
+    tokens = patchify(video, patch)
+    emb = linear(tokens, weight, bias)
+    nl, dim = lead.shape[-2], emb.shape[1]
+    x = torch.empty(b, nl + emb.shape[0] // b, dim, dtype=torch.float32, device=video.device)
+    x[:, :nl] = lead
+    x[:, nl:] = emb.view(b, -1, dim)
+    return tokens, x
+
+
+def add_position_embedding(x, pos, nk, pe_type):
+    """TokenPose's token matrix x (b, nk + n, dim) plus its position embedding: the sine tables (1, n, dim) cover the patch
+    rows only (added into x, which is returned), the learnable one (1, n + nk, dim) every row (a fresh tensor)."""
+    b, ntok, _ = x.shape
+    if pe_type in ("sine", "sine-full"):
+        x[:, nk:] = ops.add(x[:, nk:].contiguous(), pos[:, :ntok - nk].expand(b, -1, -1).contiguous())
+        return x
+    return ops.add(x, pos[:, :ntok].expand(b, -1, -1).contiguous())
+
+
+def time_perm(t, f, n):
+    """[cls | (f, n) frame-major rows] -> [cls | (n, f)]: the time attention's groups become contiguous (a copy)."""
+    b, ntok, d = t.shape
+    o = torch.empty_like(t)
+    o[:, :1] = t[:, :1]
+    o[:, 1:] = t[:, 1:].view(b, f, n, d).transpose(1, 2).reshape(b, n * f, d)
+    return o
+
+
+def time_unperm(t, f, n):
+    """Inverse (and adjoint) of time_perm."""
+    b, ntok, d = t.shape
+    o = torch.empty_like(t)
+    o[:, :1] = t[:, :1]
+    o[:, 1:] = t[:, 1:].view(b, n, f, d).transpose(1, 2).reshape(b, f * n, d)
+    return o

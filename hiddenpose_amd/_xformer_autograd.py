@@ -4,7 +4,8 @@ what the backward needs, and whose backward is a chain of HIP kernels (include/h
 backward").  PyTorch only allocates, zero-fills and copies.
 
 The op-level helpers (layernorm_backward, linear_backward, geglu_backward, gelu_backward) are written for any row-major
-token matrix; the sublayer helpers (pre-norm attention, GEGLU / GELU feed-forward) serve TimeSformer and TokenPose-L.
+token matrix; all three Functions are built from the same sublayer helpers (pre-norm attention, GEGLU / GELU feed-forward)
+and the token assembly of _xformer.embed_tokens with its adjoint.
 
 Dropout.  Every nn.Dropout of the reference modules is a *site*: its position in the reference's forward
 order.  A Function takes `drop`, None or (seed, step, p, p) with the module's two probabilities; a sublayer helper takes
@@ -17,10 +18,8 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-
-
-def _st(t):
-    return _lib.current_stream_handle(t.device)
+from . import _xformer as X
+from ._xformer import _st
 
 
 def _ws(nbytes, dev):
@@ -42,6 +41,24 @@ def active_dropout(m, p0, p1):
     if not m.training or not (p0 > 0 or p1 > 0) or not isinstance(seed, int) or isinstance(seed, bool):
         return None
     return (seed, int(m.dropout_step), float(p0), float(p1))
+
+
+def training_gate(m, x, params, p0, p1, head, p0_name, p1_name):
+    """(build an autograd graph?, drop) of a head's forward on input x.  A graph is built with dropout active (under no_grad
+    too), or when grad mode is on, the module is in training mode or x requires grad, and x or one of `params` requires
+    grad.  A graph without a seed while one of the two probabilities is > 0 is refused."""
+    drop = active_dropout(m, p0, p1)
+    graph = drop is not None or (torch.is_grad_enabled() and (m.training or x.requires_grad)
+                                 and (x.requires_grad or any(p.requires_grad for p in params)))
+    if graph and drop is None and (m.dropout_seed is None or m.training) and (p0 > 0 or p1 > 0):
+        raise _lib.HiddenPoseHipError(f"{head} training: dropout is not built without a seed ({p0_name} / {p1_name} must be 0; "
+                                      "set dropout_seed to enable)")
+    return graph, drop
+
+
+def _split(drop):
+    """A Function's (seed, step, p0, p1) -> its two sublayer tuples (seed, step, p0), (seed, step, p1); None -> None, None."""
+    return (None, None) if drop is None else ((drop[0], drop[1], drop[2]), (drop[0], drop[1], drop[3]))
 
 
 def _dropping(drop):
@@ -125,206 +142,44 @@ def geglu_backward(u, dg, drop=None, site=0):
     return du
 
 
-def attention_backward(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, frames, precision=0):
-    """(dQ, dK, dK0, dV).  precision 0: the exact-fp32 backward; 1 (bf16) / 4 (fp16): the patch queries' part on the 16-bit
-    matrix cores (hp_sformer_attention_backward_p; dim_head 32 or 64), the joint queries' part exact fp32."""
+def attention_backward(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, frames, precision=0, key_mask=None,
+                       mask_patch_queries=False, grouped=False):
+    """(dQ, dK, dK0, dV): the one place that chooses among the backward entries and sizes their workspace.  precision 0: the
+    exact-fp32 backward; 1 (bf16) / 4 (fp16): the patch queries' part on the 16-bit matrix cores (dim_head 32 or 64), the
+    joint queries' part exact fp32.  key_mask / mask_patch_queries: the forward's (a 16-bit precision needs mask_patch_queries
+    False).  grouped: the fp32 entry for n <= 64 tokens per group at dim_head 16 / 24 / 32, bit-equal to the generic one."""
     L = _lib.lib()
+    assert not (grouped and precision), "the grouped attention backward is exact fp32"
+    masked = key_mask is not None
+    if precision:
+        entry, size = ((L.hp_sformer_attention_backward_masked_p, L.hp_sformer_attention_backward_masked_p_workspace_bytes) if masked
+                       else (L.hp_sformer_attention_backward_p, L.hp_sformer_attention_backward_p_workspace_bytes))
+    elif grouped:
+        entry, size = ((L.hp_sformer_attention_backward_grouped_masked, L.hp_sformer_attention_backward_grouped_masked_workspace_bytes)
+                       if masked else (L.hp_sformer_attention_backward_grouped, L.hp_sformer_attention_backward_grouped_workspace_bytes))
+    else:
+        entry, size = ((L.hp_sformer_attention_backward_masked, L.hp_sformer_attention_backward_masked_workspace_bytes) if masked
+                       else (L.hp_sformer_attention_backward, L.hp_sformer_attention_backward_workspace_bytes))
+    mask = (key_mask.data_ptr(), int(bool(mask_patch_queries))) if masked else ()
+    prec = (precision,) if precision else ()
     dq, dk, dk0, dv = (torch.empty_like(q) for _ in range(4))
-    if precision == 0:
-        nb = L.hp_sformer_attention_backward_workspace_bytes(b, heads, dh, ntok, nj, frames)
-        ws = _ws(nb, q.device)
-        _lib.check(L.hp_sformer_attention_backward(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                                   lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), b, heads, dh, ntok,
-                                                   nj, n, frames, ws.data_ptr(), nb, _st(q)), "hp_sformer_attention_backward")
-        return dq, dk, dk0, dv
-    nb = L.hp_sformer_attention_backward_p_workspace_bytes(b, heads, dh, ntok, nj, frames, precision)
+    nb = size(b, heads, dh, ntok, nj, frames, *prec)
     ws = _ws(nb, q.device)
-    _lib.check(L.hp_sformer_attention_backward_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                                 lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), b, heads, dh, ntok,
-                                                 nj, n, frames, precision, ws.data_ptr(), nb, _st(q)), "hp_sformer_attention_backward_p")
+    _lib.check(entry(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                     dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), b, heads, dh, ntok, nj, n, frames, *mask, *prec,
+                     ws.data_ptr(), nb, _st(q)), entry.__name__)
     return dq, dk, dk0, dv
 
 
-def _layer_params(layer):
-    _time_attn, spatial, ff = layer
-    a = spatial.fn
-    return [spatial.norm.weight, spatial.norm.bias, a.to_qkv.weight, a.to_out[0].weight, a.to_out[0].bias, ff.norm.weight,
-            ff.norm.bias, ff.fn.net[0].weight, ff.fn.net[0].bias, ff.fn.net[3].weight, ff.fn.net[3].bias]
-
-
-PER_LAYER = 11
-
-
-def trainable_params(m):
-    """The parameters the forward reads, in the order SformerFunction takes them (the time-attention weights, allocated
-    but never run, are not among them: their .grad stays None)."""
-    ps = [m.to_patch_embedding.weight, m.to_patch_embedding.bias, m.joints_token]
-    for layer in m.layers:
-        ps += _layer_params(layer)
-    ps += [m.to_out[0].weight, m.to_out[0].bias, m.to_out[1].weight, m.to_out[1].bias]
-    return ps
-
-
-class SformerFunction(torch.autograd.Function):
-    """video (b, f, c, H, W), module, three precisions, drop, *trainable_params(m) -> (b, num_joints, 4, out_dim / 4).
-    drop: None or (seed, step, attn_dropout, ff_dropout); sites per layer: 2 i the spatial attention's to_out, 2 i + 1 the
-    feed-forward's hidden activation (the time attention is never run and has no site)."""
-
-    @staticmethod
-    def forward(ctx, video, m, prec, aprec, bprec, drop, *params):
-        """prec, aprec, bprec: HP_PRECISION_* of the Linear layers, the patch attention's forward and the attention backward."""
-        d_attn = None if drop is None else (drop[0], drop[1], drop[2])
-        d_ff = None if drop is None else (drop[0], drop[1], drop[3])
-        L = _lib.lib()
-        b, f, c, H, W = video.shape
-        ps, nj, heads, dh = m.patch_size, m.num_joints, m.heads, m.dim_head
-        hp, wp = H // ps, W // ps
-        n = hp * wp
-        ntok = nj + f * n
-        dim = m.joints_token.shape[-1]
-        dev = video.device
-        st = _st(video)
-        pe_w, pe_b, jtok = params[:3]
-        tokens = torch.empty(b * f * n, ps * ps * c, dtype=torch.float32, device=dev)
-        _lib.check(L.hp_sformer_patchify(video.data_ptr(), tokens.data_ptr(), b, f, c, H, W, ps, st), "hp_sformer_patchify")
-        emb = linear(tokens, pe_w, pe_b)
-        x = torch.empty(b, ntok, dim, dtype=torch.float32, device=dev)
-        x[:, :nj] = jtok
-        x[:, nj:] = emb.view(b, f * n, dim)
-        sin_t, cos_t = m.image_rot_emb.tables(hp, wp, dev)
-        rot_dim = sin_t.shape[-1]
-        rows = b * ntok
-        inner = heads * dh
-        aws = torch.empty(int(L.hp_sformer_attention_workspace_bytes(b, heads, dh)) // 4, dtype=torch.float32, device=dev)
-        saved = []
-        for i, layer in enumerate(m.layers):
-            ln1_w, ln1_b, wqkv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2 = params[3 + PER_LAYER * i: 3 + PER_LAYER * (i + 1)]
-            scale, eps1, eps2 = layer[1].fn.scale, layer[1].norm.eps, layer[2].norm.eps
-            h1 = torch.empty_like(x)
-            _lib.check(L.hp_layernorm_forward(x.data_ptr(), h1.data_ptr(), rows, dim, ln1_w.data_ptr(), ln1_b.data_ptr(), eps1, 0, 0, st),
-                       "hp_layernorm_forward")
-            qkv = linear(h1.view(rows, dim), wqkv, None, prec)
-            q = torch.empty(b, heads, ntok, dh, dtype=torch.float32, device=dev)
-            k, k0, v = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-            _lib.check(L.hp_sformer_qkv_prepare(qkv.data_ptr(), q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), b, ntok, heads, dh,
-                                                nj, n, scale, sin_t.data_ptr(), cos_t.data_ptr(), rot_dim, st), "hp_sformer_qkv_prepare")
-            del qkv
-            att = torch.empty(b, ntok, inner, dtype=torch.float32, device=dev)
-            lse = None
-            if aprec == 0:
-                lse = torch.empty(b, heads, ntok, dtype=torch.float32, device=dev)
-                _lib.check(L.hp_sformer_attention_lse(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(),
-                                                      b, heads, dh, ntok, nj, n, f, aws.data_ptr(), st), "hp_sformer_attention_lse")
-            elif bprec != 0:   # a 16-bit backward recomputes P from the 16-bit forward's own lse
-                lse = torch.empty(b, heads, ntok, dtype=torch.float32, device=dev)
-                _lib.check(L.hp_sformer_attention_lse_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(),
-                                                        b, heads, dh, ntok, nj, n, f, aprec, aws.data_ptr(), st), "hp_sformer_attention_lse_p")
-            else:
-                _lib.check(L.hp_sformer_attention(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), b, heads, dh,
-                                                  ntok, nj, n, f, aprec, aws.data_ptr(), st), "hp_sformer_attention")
-            if _dropping(d_attn):
-                x1 = linear(att.view(rows, inner), wo, bo, prec)
-                x1 = dropout(x1, d_attn, 2 * i, addend=x).view(b, ntok, dim)
-            else:
-                x1 = linear(att.view(rows, inner), wo, bo, prec, addend=x.view(rows, dim)).view(b, ntok, dim)
-            h2 = torch.empty_like(x)
-            _lib.check(L.hp_layernorm_forward(x1.data_ptr(), h2.data_ptr(), rows, dim, ln2_w.data_ptr(), ln2_b.data_ptr(), eps2, 0, 0, st),
-                       "hp_layernorm_forward")
-            hid = w2.shape[1]
-            g = torch.empty(rows, hid, dtype=torch.float32, device=dev)
-            if hid % 64 == 0 and w1.shape[0] == 2 * hid:   # as _xformer.geglu_ff: the GEGLU in the GEMM's epilogue
-                _lib.check(L.hp_linear_geglu_forward(h2.data_ptr(), w1.data_ptr(), _lib.ptr(b1), g.data_ptr(), rows, dim, 2 * hid, prec, st),
-                           "hp_linear_geglu_forward")
-            else:
-                u = linear(h2.view(rows, dim), w1, b1, prec)
-                _lib.check(L.hp_geglu_forward(u.data_ptr(), g.data_ptr(), rows, hid, st), "hp_geglu_forward")
-                del u
-            if _dropping(d_ff):
-                dropout(g, d_ff, 2 * i + 1)     # the saved activation is the dropped one: what W2's gradient needs
-            x2 = linear(g, w2, b2, prec, addend=x1.view(rows, dim)).view(b, ntok, dim)
-            saved += [x, h1, q, k, k0, v, att, lse, x1, h2, g]
-            x = x2
-        jt = torch.empty(b * nj, dim, dtype=torch.float32, device=dev)
-        _lib.check(L.hp_layernorm_forward(x.data_ptr(), jt.data_ptr(), b * nj, dim, params[-4].data_ptr(), params[-3].data_ptr(),
-                                          m.to_out[0].eps, nj, ntok, st), "hp_layernorm_forward")
-        out = linear(jt, params[-2], params[-1])
-        ctx.geom = (b, f, c, H, W, ps, nj, heads, dh, n, ntok, dim, rot_dim, prec, aprec, bprec)
-        ctx.consts = [(layer[1].fn.scale, layer[1].norm.eps, layer[2].norm.eps) for layer in m.layers] + [m.to_out[0].eps]
-        ctx.depth = len(m.layers)
-        ctx.drops = (d_attn, d_ff)
-        ctx.nsaved = len(saved)
-        ctx.save_for_backward(*saved, tokens, x, jt, sin_t, cos_t, *params)
-        return out.view(b, nj, 4, -1)
-
-    @staticmethod
-    def backward(ctx, dout):
-        b, f, c, H, W, ps, nj, heads, dh, n, ntok, dim, rot_dim, prec, aprec, bprec = ctx.geom
-        if aprec != 0 and bprec == 0:
-            raise _lib.HiddenPoseHipError("NlosPoseSformer backward: training needs attention_precision = \"fp32\" (the bf16 / fp16 "
-                                          "patch attention has no fp32 backward) or attention_backward_precision = \"bf16\" / "
-                                          "\"fp16\"")
-        L = _lib.lib()
-        allt = ctx.saved_tensors
-        saved, (tokens, xl, jt, sin_t, cos_t), params = allt[:ctx.nsaved], allt[ctx.nsaved:ctx.nsaved + 5], allt[ctx.nsaved + 5:]
-        dev = dout.device
-        st = _st(dout)
-        rows, inner = b * ntok, heads * dh
-        d_attn, d_ff = ctx.drops
-        grads = [None] * len(params)
-        dout = dout.contiguous().view(b * nj, -1)
-        # head: LN(x[:, :nj]) -> Linear
-        djt, grads[-2], grads[-1] = linear_backward(jt, dout, params[-2])
-        dx = torch.zeros(b, ntok, dim, dtype=torch.float32, device=dev)
-        grads[-4], grads[-3] = layernorm_backward(xl, djt, dx, params[-4], ctx.consts[-1], b * nj, dim, nj, ntok)
-        for i in reversed(range(ctx.depth)):
-            x, h1, q, k, k0, v, att, lse, x1, h2, g = saved[11 * i: 11 * (i + 1)]
-            base = 3 + PER_LAYER * i
-            ln1_w, ln1_b, wqkv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2 = params[base: base + PER_LAYER]
-            scale, eps1, eps2 = ctx.consts[i]
-            # feed-forward: x2 = x1 + W2 (a * gelu(t)) + b2, [a | t] = u = W1 LN2(x1) + b1
-            d2 = dx.view(rows, dim)
-            dg, grads[base + 9], grads[base + 10] = linear_backward(g, d2, w2, prec)
-            u = linear(h2.view(rows, dim), w1, b1, prec)
-            du = geglu_backward(u, dg, d_ff, 2 * i + 1)
-            del u, dg
-            dh2, grads[base + 7], grads[base + 8] = linear_backward(h2.view(rows, dim), du, w1, prec)
-            del du
-            grads[base + 5], grads[base + 6] = layernorm_backward(x1, dh2, dx, ln2_w, eps2, rows, dim)   # dx := dx1
-            del dh2
-            # attention: x1 = x + Wo att + bo
-            dlin = dropout(d2, d_attn, 2 * i, out=torch.empty_like(d2)) if _dropping(d_attn) else d2
-            datt, grads[base + 3], grads[base + 4] = linear_backward(att.view(rows, inner), dlin, wo, prec)
-            del dlin
-            dq, dk, dk0, dv = attention_backward(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, f, bprec)
-            del datt
-            dqkv = torch.empty(rows, 3 * inner, dtype=torch.float32, device=dev)
-            _lib.check(L.hp_sformer_qkv_prepare_backward(dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), dqkv.data_ptr(), b,
-                                                         ntok, heads, dh, nj, n, scale, sin_t.data_ptr(), cos_t.data_ptr(), rot_dim, st),
-                       "hp_sformer_qkv_prepare_backward")
-            del dq, dk, dk0, dv
-            dh1, grads[base + 2], _ = linear_backward(h1.view(rows, dim), dqkv, wqkv, prec, with_bias=False)
-            del dqkv
-            grads[base], grads[base + 1] = layernorm_backward(x, dh1, dx, ln1_w, eps1, rows, dim)   # dx := dx of the layer input
-            del dh1
-        # token assembly: joints_token is shared by the batch; the patch rows go back through the embedding and patchify
-        djtok = torch.empty(1, nj, dim, dtype=torch.float32, device=dev)
-        _lib.check(L.hp_sformer_joint_token_backward(dx.data_ptr(), djtok.data_ptr(), b, nj, ntok, dim, st),
-                   "hp_sformer_joint_token_backward")
-        grads[2] = djtok
-        demb = dx[:, nj:].contiguous().view(b * f * n, dim)
-        need_video = ctx.needs_input_grad[0]
-        dtok, grads[0], grads[1] = linear_backward(tokens, demb, params[0], need_dx=need_video)
-        dvideo = None
-        if need_video:
-            dvideo = torch.empty(b, f, c, H, W, dtype=torch.float32, device=dev)
-            _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dvideo.data_ptr(), b, f, c, H, W, ps, st), "hp_sformer_unpatchify")
-        return (dvideo, None, None, None, None, None, *grads)
+def attention_backward_grouped(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, groups):
+    """attention_backward for short groups: n <= 64 tokens per group."""
+    return attention_backward(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, groups, grouped=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# TimeSformer and TokenPose-L training paths.  The sublayer helpers below take the layer input x (b, ntok, dim) and return a
-# fresh x + sublayer(x) together with what their backward needs; their backward ADDS the sublayer's input gradient into dx
-# (the residual stream's gradient, which already holds d(x + sublayer(x))) and returns the parameter gradients.
+# The sublayer helpers of the three heads' training paths take the layer input x (b, ntok, dim) and return a fresh
+# x + sublayer(x) together with what their backward needs; their backward ADDS the sublayer's input gradient into dx (the
+# residual stream's gradient, which already holds d(x + sublayer(x))) and returns the parameter gradients.
 
 FP32_BACKWARD_AFTER_16BIT_FORWARD = ("{} backward: training needs attention_precision = \"fp32\" (the bf16 / fp16 patch attention "
                                      "has no fp32 backward) or attention_backward_precision = \"bf16\" / \"fp16\"")
@@ -342,67 +197,10 @@ def gelu_backward(u, dy, drop=None, site=0):
     return dy
 
 
-def attention_backward_masked(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, groups, key_mask, mask_patch_queries,
-                              grouped=False, precision=0):
-    """(dQ, dK, dK0, dV) of the fp32 attention with a key mask (hp_sformer_attention_backward_masked, or its grouped form
-    for n <= 64 tokens per group at dim_head 16 / 24 / 32; the two are bit-equal).  precision 1 (bf16) / 4 (fp16):
-    hp_sformer_attention_backward_masked_p (the patch queries on the 16-bit matrix cores; not grouped, mask_patch_queries False)."""
-    L = _lib.lib()
-    dq, dk, dk0, dv = (torch.empty_like(q) for _ in range(4))
-    if precision != 0:
-        assert not grouped, "the grouped attention backward is exact fp32"
-        nb = L.hp_sformer_attention_backward_masked_p_workspace_bytes(b, heads, dh, ntok, nj, groups, precision)
-        ws = _ws(nb, q.device)
-        _lib.check(L.hp_sformer_attention_backward_masked_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(),
-                                                            dout.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(),
-                                                            dv.data_ptr(), b, heads, dh, ntok, nj, n, groups, key_mask.data_ptr(),
-                                                            int(bool(mask_patch_queries)), precision, ws.data_ptr(), nb, _st(q)),
-                   "hp_sformer_attention_backward_masked_p")
-        return dq, dk, dk0, dv
-    name = "hp_sformer_attention_backward_grouped_masked" if grouped else "hp_sformer_attention_backward_masked"
-    nb = getattr(L, name + "_workspace_bytes")(b, heads, dh, ntok, nj, groups)
-    ws = _ws(nb, q.device)
-    _lib.check(getattr(L, name)(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
-                                dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(), dv.data_ptr(), b, heads, dh, ntok, nj, n, groups,
-                                key_mask.data_ptr(), int(bool(mask_patch_queries)), ws.data_ptr(), nb, _st(q)), name)
-    return dq, dk, dk0, dv
-
-
-def attention_backward_grouped(q, k, k0, v, out, dout, lse, b, heads, dh, ntok, nj, n, groups):
-    """attention_backward for short groups (hp_sformer_attention_backward_grouped): n <= 64 tokens per group."""
-    L = _lib.lib()
-    dq, dk, dk0, dv = (torch.empty_like(q) for _ in range(4))
-    nb = L.hp_sformer_attention_backward_grouped_workspace_bytes(b, heads, dh, ntok, nj, groups)
-    ws = _ws(nb, q.device)
-    _lib.check(L.hp_sformer_attention_backward_grouped(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), out.data_ptr(),
-                                                       dout.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dk0.data_ptr(),
-                                                       dv.data_ptr(), b, heads, dh, ntok, nj, n, groups, ws.data_ptr(), nb, _st(q)),
-               "hp_sformer_attention_backward_grouped")
-    return dq, dk, dk0, dv
-
-
-# time attention's backward: "grouped" (hp_sformer_attention_backward_grouped) or "generic" (hp_sformer_attention_backward);
-# DESIGN 4.4.2 records the A/B that chose it
+# time attention's backward: "grouped" (attention_backward's grouped entry) or "generic"; DESIGN 4.4.2 records the A/B that
+# chose it
 TIME_ATTENTION_BACKWARD = "grouped"
 GROUPED_DIM_HEADS = (16, 24, 32)   # the grouped entry is not built for dim_head 64: that width takes the generic one
-
-
-def time_perm(t, f, n):
-    """[cls | (f, n) frame-major rows] -> [cls | (n, f)]: the time attention's groups become contiguous (a copy)."""
-    b, ntok, d = t.shape
-    o = torch.empty_like(t)
-    o[:, :1] = t[:, :1]
-    o[:, 1:] = t[:, 1:].view(b, f, n, d).transpose(1, 2).reshape(b, n * f, d)
-    return o
-
-
-def time_unperm(t, f, n):
-    """Inverse (and adjoint) of time_perm."""
-    b, ntok, d = t.shape
-    o = torch.empty_like(t)
-    o[:, :1] = t[:, :1]
-    o[:, 1:] = t[:, 1:].view(b, n, f, d).transpose(1, 2).reshape(b, f * n, d)
-    return o
 
 
 def token_shift_adjoint(g, frames, nj=1):
@@ -429,17 +227,16 @@ def layernorm(x, w, b, eps, rows, dim, rows_per_batch=0, batch_stride_rows=0):
 
 
 def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t, cos_t, prec, pre=None, perm=None, unperm=None,
-                              key_mask=None, mask_patch_queries=False, aprec=0, drop=None, site=0):
+                              key_mask=None, mask_patch_queries=False, aprec=0, drop=None, site=0, need_lse=True):
     """x + Wo unperm(Attn(perm(pre(LN(x))))) + bo for the token layout [nj | groups x n] of the permuted rows, as
-    _xformer.attention runs it (with lse; key_mask (b, ntok) uint8 in the permuted rows' order selects
-    hp_sformer_attention_lse_masked).  aprec: HP_PRECISION_* of the patch queries (0; 1 / 4 take the _p entries).
+    _xformer.attention runs it, but with the soft-max's lse unless need_lse is False (the backward then has nothing to
+    recompute P from); key_mask (b, ntok) uint8 in the permuted rows' order.  aprec: HP_PRECISION_* of the patch queries.
     p = (ln_w, ln_b, wqkv, wo, bo).  drop / site: dropout on to_out's output, before the residual.  -> (x1, saved)."""
     L = _lib.lib()
     ln_w, ln_b, wqkv, wo, bo = p
     b, ntok, dim = x.shape
     rows, inner = b * ntok, heads * dh
     dev = x.device
-    st = _st(x)
     h = layernorm(x, ln_w, ln_b, eps, rows, dim).view(b, ntok, dim)
     if pre is not None:
         h = pre(h)
@@ -450,27 +247,12 @@ def prenorm_attention_forward(x, p, eps, scale, heads, dh, nj, n, groups, sin_t,
     k, k0, v = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
     rot_dim = 0 if sin_t is None else sin_t.shape[-1]
     _lib.check(L.hp_sformer_qkv_prepare(qkv.data_ptr(), q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), b, ntok, heads, dh, nj, n,
-                                        scale, _lib.ptr(sin_t), _lib.ptr(cos_t), rot_dim, st), "hp_sformer_qkv_prepare")
+                                        scale, _lib.ptr(sin_t), _lib.ptr(cos_t), rot_dim, _st(x)), "hp_sformer_qkv_prepare")
     del qkv
     att = torch.empty(b, ntok, inner, dtype=torch.float32, device=dev)
-    lse = torch.empty(b, heads, ntok, dtype=torch.float32, device=dev)
-    aws = _ws(L.hp_sformer_attention_workspace_bytes(b, heads, dh), dev)
-    if key_mask is None and aprec == 0:
-        _lib.check(L.hp_sformer_attention_lse(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(), b,
-                                              heads, dh, ntok, nj, n, groups, aws.data_ptr(), st), "hp_sformer_attention_lse")
-    elif key_mask is None:
-        _lib.check(L.hp_sformer_attention_lse_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(), lse.data_ptr(), b,
-                                                heads, dh, ntok, nj, n, groups, aprec, aws.data_ptr(), st), "hp_sformer_attention_lse_p")
-    elif aprec != 0:
-        _lib.check(L.hp_sformer_attention_lse_masked_p(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(),
-                                                       lse.data_ptr(), b, heads, dh, ntok, nj, n, groups, key_mask.data_ptr(),
-                                                       int(bool(mask_patch_queries)), aprec, aws.data_ptr(), st),
-                   "hp_sformer_attention_lse_masked_p")
-    else:
-        _lib.check(L.hp_sformer_attention_lse_masked(q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), att.data_ptr(),
-                                                     lse.data_ptr(), b, heads, dh, ntok, nj, n, groups, key_mask.data_ptr(),
-                                                     int(bool(mask_patch_queries)), aws.data_ptr(), st),
-                   "hp_sformer_attention_lse_masked")
+    lse = torch.empty(b, heads, ntok, dtype=torch.float32, device=dev) if need_lse else None
+    X.attention_forward(q, k, k0, v, att, lse, b, heads, dh, ntok, nj, n, groups, X.attention_workspace(b, heads, dh, dev), key_mask,
+                        mask_patch_queries, aprec)
     ab = unperm(att) if unperm is not None else att
     if _dropping(drop):
         x1 = linear(ab.view(rows, inner), wo, bo, prec)
@@ -496,15 +278,8 @@ def prenorm_attention_backward(dx, saved, p, eps, scale, heads, dh, nj, n, group
     del dlin
     datt = perm(dab.view(b, ntok, inner)) if perm is not None else dab     # the adjoint of unperm is perm
     del dab
-    if key_mask is None and bprec != 0:
-        assert not grouped, "the grouped attention backward is exact fp32"
-        dq, dk, dk0, dv = attention_backward(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups, bprec)
-    elif key_mask is None:
-        bwd = attention_backward_grouped if grouped else attention_backward
-        dq, dk, dk0, dv = bwd(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups)
-    else:
-        dq, dk, dk0, dv = attention_backward_masked(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups, key_mask,
-                                                    mask_patch_queries, grouped, bprec)
+    dq, dk, dk0, dv = attention_backward(q, k, k0, v, att, datt, lse, b, heads, dh, ntok, nj, n, groups, bprec, key_mask,
+                                         mask_patch_queries, grouped)
     del datt
     dqkv = torch.empty(rows, 3 * inner, dtype=torch.float32, device=x.device)
     rot_dim = 0 if sin_t is None else sin_t.shape[-1]
@@ -613,6 +388,108 @@ def _joint_sum(dx, rows):
     return out
 
 
+def embed_tokens_backward(dx, tokens, weight, lead_rows, video_shape, patch, need_input):
+    """Adjoint of _xformer.embed_tokens below the lead_rows leading rows of dx (b, ntok, dim): -> (dvideo (b, f, c, H, W), or
+    None unless need_input; dW; db) through the embedding's Linear and unpatchify."""
+    b, f, c, H, W = video_shape
+    demb = dx[:, lead_rows:].contiguous().view(tokens.shape[0], -1)
+    dtok, dw, db = linear_backward(tokens, demb, weight, need_dx=need_input)
+    dvideo = None
+    if need_input:
+        dvideo = torch.empty(b, f, c, H, W, dtype=torch.float32, device=dx.device)
+        _lib.check(_lib.lib().hp_sformer_unpatchify(dtok.data_ptr(), dvideo.data_ptr(), b, f, c, H, W, patch, _st(dx)),
+                   "hp_sformer_unpatchify")
+    return dvideo, dw, db
+
+
+def _layer_params(layer):
+    _time_attn, spatial, ff = layer
+    a = spatial.fn
+    return [spatial.norm.weight, spatial.norm.bias, a.to_qkv.weight, a.to_out[0].weight, a.to_out[0].bias, ff.norm.weight,
+            ff.norm.bias, ff.fn.net[0].weight, ff.fn.net[0].bias, ff.fn.net[3].weight, ff.fn.net[3].bias]
+
+
+PER_LAYER = 11
+
+
+def trainable_params(m):
+    """The parameters the forward reads, in the order SformerFunction takes them (the time-attention weights, allocated
+    but never run, are not among them: their .grad stays None)."""
+    ps = [m.to_patch_embedding.weight, m.to_patch_embedding.bias, m.joints_token]
+    for layer in m.layers:
+        ps += _layer_params(layer)
+    ps += [m.to_out[0].weight, m.to_out[0].bias, m.to_out[1].weight, m.to_out[1].bias]
+    return ps
+
+
+class SformerFunction(torch.autograd.Function):
+    """video (b, f, c, H, W), module, three precisions, drop, *trainable_params(m) -> (b, num_joints, 4, out_dim / 4).
+    Per layer: space attention (the axial tables, groups = f frames of hp*wp patches behind the num_joints joint tokens) and
+    GEGLU feed-forward.  drop: None or (seed, step, attn_dropout, ff_dropout); sites per layer: 2 i the spatial attention's
+    to_out, 2 i + 1 the feed-forward's hidden activation (the time attention is never run and has no site)."""
+
+    @staticmethod
+    def forward(ctx, video, m, prec, aprec, bprec, drop, *params):
+        """prec, aprec, bprec: HP_PRECISION_* of the Linear layers, the patch attention's forward and the attention backward."""
+        b, f, c, H, W = video.shape
+        ps, nj, heads, dh = m.patch_size, m.num_joints, m.heads, m.dim_head
+        hp, wp = H // ps, W // ps
+        n = hp * wp
+        tokens, x = X.embed_tokens(video, ps, *params[:3])
+        ntok, dim = x.shape[1:]
+        sin_t, cos_t = m.image_rot_emb.tables(hp, wp, video.device)
+        d_attn, d_ff = _split(drop)
+        # a 16-bit backward recomputes P from the 16-bit forward's own lse; a 16-bit forward with the fp32 backward (which
+        # backward() refuses) keeps none
+        need_lse = aprec == 0 or bprec != 0
+        saved, consts = [], []
+        for i, (_time_attn, spatial, ff) in enumerate(m.layers):
+            lp = params[3 + PER_LAYER * i: 3 + PER_LAYER * (i + 1)]
+            scale, e_a, e_f = spatial.fn.scale, spatial.norm.eps, ff.norm.eps
+            x, s_a = prenorm_attention_forward(x, lp[0:5], e_a, scale, heads, dh, nj, n, f, sin_t, cos_t, prec, aprec=aprec,
+                                               drop=d_attn, site=2 * i, need_lse=need_lse)
+            x, s_f = geglu_ff_forward(x, lp[5:11], e_f, prec, drop=d_ff, site=2 * i + 1)
+            saved += [*s_a, *s_f]
+            consts.append((scale, e_a, e_f))
+        jt = layernorm(x, params[-4], params[-3], m.to_out[0].eps, b * nj, dim, nj, ntok)
+        out = linear(jt, params[-2], params[-1])
+        ctx.geom = (tuple(video.shape), ps, nj, heads, dh, n, prec, aprec, bprec, m.to_out[0].eps)
+        ctx.consts = consts
+        ctx.drops = (d_attn, d_ff)
+        ctx.nsaved = len(saved)
+        ctx.save_for_backward(*saved, tokens, x, jt, sin_t, cos_t, *params)
+        return out.view(b, nj, 4, -1)
+
+    @staticmethod
+    def backward(ctx, dout):
+        video_shape, ps, nj, heads, dh, n, prec, aprec, bprec, eps_out = ctx.geom
+        if aprec != 0 and bprec == 0:
+            raise _lib.HiddenPoseHipError(FP32_BACKWARD_AFTER_16BIT_FORWARD.format("NlosPoseSformer"))
+        allt = ctx.saved_tensors
+        saved, (tokens, xl, jt, sin_t, cos_t), params = allt[:ctx.nsaved], allt[ctx.nsaved:ctx.nsaved + 5], allt[ctx.nsaved + 5:]
+        b, f = video_shape[:2]
+        ntok, dim = xl.shape[1:]
+        grads = [None] * len(params)
+        # head: LN(x[:, :nj]) -> Linear
+        djt, grads[-2], grads[-1] = linear_backward(jt, dout.contiguous().view(b * nj, -1), params[-2])
+        dx = torch.zeros(b, ntok, dim, dtype=torch.float32, device=dout.device)
+        grads[-4], grads[-3] = layernorm_backward(xl, djt, dx, params[-4], eps_out, b * nj, dim, nj, ntok)
+        del djt
+        d_attn, d_ff = ctx.drops
+        per = 9 + 3
+        for i in reversed(range(len(ctx.consts))):
+            sv = saved[per * i: per * (i + 1)]
+            base = 3 + PER_LAYER * i
+            lp = params[base: base + PER_LAYER]
+            scale, e_a, e_f = ctx.consts[i]
+            grads[base + 5: base + 11] = geglu_ff_backward(dx, sv[9:12], lp[5:11], e_f, prec, drop=d_ff, site=2 * i + 1)
+            grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_a, scale, heads, dh, nj, n, f, sin_t, cos_t, prec,
+                                                               bprec=bprec, drop=d_attn, site=2 * i)
+        grads[2] = _joint_sum(dx, nj)      # joints_token (1, nj, dim), shared by the batch
+        dvideo, grads[0], grads[1] = embed_tokens_backward(dx, tokens, params[0], nj, video_shape, ps, ctx.needs_input_grad[0])
+        return (dvideo, None, None, None, None, None, *grads)
+
+
 def _unwrap(m, shift):
     return m.fn if shift else m
 
@@ -647,28 +524,19 @@ class TimeSformerFunction(torch.autograd.Function):
         the class queries are exact fp32)."""
         from .transformer import _token_shift
 
-        L = _lib.lib()
         b, f, c, H, W = video.shape
         ps, heads, dh = m.patch_size, m.heads, m.dim_head
         hp, wp = H // ps, W // ps
         n = hp * wp
-        ntok = 1 + f * n
-        dim = m.cls_token.shape[-1]
         dev = video.device
-        tokens = torch.empty(b * f * n, ps * ps * c, dtype=torch.float32, device=dev)
-        _lib.check(L.hp_sformer_patchify(video.data_ptr(), tokens.data_ptr(), b, f, c, H, W, ps, _st(video)), "hp_sformer_patchify")
-        emb = linear(tokens, params[0], params[1])
-        x = torch.empty(b, ntok, dim, dtype=torch.float32, device=dev)
-        x[:, :1] = params[2]
-        x[:, 1:] = emb.view(b, f * n, dim)
-        del emb
+        tokens, x = X.embed_tokens(video, ps, *params[:3])
+        ntok, dim = x.shape[1:]
         sin_s, cos_s = m.image_rot_emb.tables(hp, wp, dev)
         sin_t, cos_t = m._frame_tables(f, dev)
         pre = (lambda t: _token_shift(t, f)) if m.shift_tokens else None
-        perm, unperm = (lambda t: time_perm(t, f, n)), (lambda t: time_unperm(t, f, n))
+        perm, unperm = (lambda t: X.time_perm(t, f, n)), (lambda t: X.time_unperm(t, f, n))
         saved, consts = [], []
-        d_attn = None if drop is None else (drop[0], drop[1], drop[2])
-        d_ff = None if drop is None else (drop[0], drop[1], drop[3])
+        d_attn, d_ff = _split(drop)
         for i, (time_attn, spatial, ff) in enumerate(m.layers):
             lp = params[3 + TS_PER_LAYER * i: 3 + TS_PER_LAYER * (i + 1)]
             sc_t, sc_s = _unwrap(time_attn.fn, m.shift_tokens).scale, _unwrap(spatial.fn, m.shift_tokens).scale
@@ -682,7 +550,7 @@ class TimeSformerFunction(torch.autograd.Function):
             consts.append((sc_t, sc_s) + eps)
         cls = layernorm(x, params[-4], params[-3], m.to_out[0].eps, b, dim, 1, ntok)
         out = linear(cls, params[-2], params[-1])
-        ctx.geom = (b, f, c, H, W, ps, heads, dh, n, ntok, dim, prec, m.shift_tokens, m.to_out[0].eps)
+        ctx.geom = (tuple(video.shape), ps, heads, dh, n, prec, m.shift_tokens, m.to_out[0].eps)
         ctx.aprecs = (aprec, bprec)
         ctx.consts = consts
         ctx.drops = (d_attn, d_ff)
@@ -693,15 +561,16 @@ class TimeSformerFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        b, f, c, H, W, ps, heads, dh, n, ntok, dim, prec, shift, eps_out = ctx.geom
+        video_shape, ps, heads, dh, n, prec, shift, eps_out = ctx.geom
         aprec, bprec = ctx.aprecs
         if aprec != 0 and bprec == 0:
             raise _lib.HiddenPoseHipError(FP32_BACKWARD_AFTER_16BIT_FORWARD.format("TimeSformer"))
-        L = _lib.lib()
         allt = ctx.saved_tensors
         saved = allt[:ctx.nsaved]
         tokens, xl, cls, sin_s, cos_s, sin_t, cos_t = allt[ctx.nsaved:ctx.nsaved + 7]
         params = allt[ctx.nsaved + 7:]
+        b, f = video_shape[:2]
+        ntok, dim = xl.shape[1:]
         dev = dout.device
         grads = [None] * len(params)
         dout = dout.contiguous()
@@ -710,7 +579,7 @@ class TimeSformerFunction(torch.autograd.Function):
         grads[-4], grads[-3] = layernorm_backward(xl, dcls, dx, params[-4], eps_out, b, dim, 1, ntok)
         del dcls
         pre_adj = (lambda t: token_shift_adjoint(t, f)) if shift else None
-        perm, unperm = (lambda t: time_perm(t, f, n)), (lambda t: time_unperm(t, f, n))
+        perm, unperm = (lambda t: X.time_perm(t, f, n)), (lambda t: X.time_unperm(t, f, n))
         grouped = TIME_ATTENTION_BACKWARD == "grouped" and dh in GROUPED_DIM_HEADS
         mask_nat, mask_time = ctx.masks
         d_attn, d_ff = ctx.drops
@@ -728,13 +597,7 @@ class TimeSformerFunction(torch.autograd.Function):
                                                                pre_adj, perm, unperm, grouped=grouped, key_mask=mask_time,
                                                                mask_patch_queries=True, drop=d_attn, site=3 * i)
         grads[2] = _joint_sum(dx, 1).view(1, dim)      # cls_token (1, dim), shared by the batch
-        demb = dx[:, 1:].contiguous().view(b * f * n, dim)
-        need_video = ctx.needs_input_grad[0]
-        dtok, grads[0], grads[1] = linear_backward(tokens, demb, params[0], need_dx=need_video)
-        dvideo = None
-        if need_video:
-            dvideo = torch.empty(b, f, c, H, W, dtype=torch.float32, device=dev)
-            _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dvideo.data_ptr(), b, f, c, H, W, ps, _st(dout)), "hp_sformer_unpatchify")
+        dvideo, grads[0], grads[1] = embed_tokens_backward(dx, tokens, params[0], 1, video_shape, ps, ctx.needs_input_grad[0])
         return (dvideo, None, None, None, None, None, None, None, *grads)
 
 
@@ -763,28 +626,12 @@ class TokenPoseFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feature, m, prec, aprec, bprec, drop, *params):
         """aprec, bprec: HP_PRECISION_* of the attention (every token is a patch query), forward and backward."""
-        d_lay = None if drop is None else (drop[0], drop[1], drop[2])
-        d_emb = None if drop is None else (drop[0], drop[1], drop[3])
-        from . import hip_ops as ops
-
-        L = _lib.lib()
+        d_lay, d_emb = _split(drop)
         b, c, H, W = feature.shape
-        nk, dim, ps = m.num_keypoints, m.keypoint_token.shape[-1], m.patch_size[0]
-        dev = feature.device
-        tok = torch.empty(b * (H // ps) * (W // ps), ps * ps * c, dtype=torch.float32, device=dev)
-        _lib.check(L.hp_sformer_patchify(feature.data_ptr(), tok.data_ptr(), b, 1, c, H, W, ps, _st(feature)), "hp_sformer_patchify")
-        emb = linear(tok, params[0], params[1]).view(b, -1, dim)
-        n = emb.shape[1]
-        ntok = nk + n
-        pos = params[3]
-        x = torch.empty(b, ntok, dim, dtype=torch.float32, device=dev)
-        x[:, :nk] = params[2]
-        if m.pos_embedding_type in ("sine", "sine-full"):
-            x[:, nk:] = ops.add(emb.contiguous(), pos[:, :n].expand(b, -1, -1).contiguous())
-        else:
-            x[:, nk:] = emb
-            x = ops.add(x, pos[:, :n + nk].expand(b, -1, -1).contiguous())
-        del emb
+        nk, ps, pos = m.num_keypoints, m.patch_size[0], params[3]
+        tok, x = X.embed_tokens(feature.view(b, 1, c, H, W), ps, *params[:3])
+        x = X.add_position_embedding(x, pos, nk, m.pos_embedding_type)
+        ntok, dim = x.shape[1:]
         if _dropping(d_emb):
             dropout(x, d_emb, 0)
         saved, consts, outs = [], [], []
@@ -793,8 +640,7 @@ class TokenPoseFunction(torch.autograd.Function):
             for idx, (attn, ff) in enumerate(t.layers):
                 lp = params[4 + TP_PER_LAYER * i: 4 + TP_PER_LAYER * (i + 1)]
                 if idx > 0 and t.all_attn:   # 'sine-full': the (frozen) table re-added to the patch rows
-                    x = x.clone()
-                    x[:, nk:] = ops.add(x[:, nk:].contiguous(), pos.expand(b, -1, -1).contiguous())
+                    x = X.add_position_embedding(x.clone(), pos, nk, m.pos_embedding_type)
                 a = attn.fn.fn
                 dh = dim // a.heads
                 x, s_a = prenorm_attention_forward(x, lp[0:5], attn.fn.norm.eps, a.scale, a.heads, dh, 0, ntok, 1, None, None, prec,
@@ -808,7 +654,7 @@ class TokenPoseFunction(torch.autograd.Function):
         y = layernorm(cat, params[-4], params[-3], m.mlp_head[0].eps, b * nk, 3 * dim)
         out = linear(y, params[-2], params[-1])
         depths = [len(t.layers) for t in (m.transformer1, m.transformer2, m.transformer3)]
-        ctx.geom = (b, c, H, W, ps, nk, n, ntok, dim, prec, m.pos_embedding_type, m.mlp_head[0].eps, depths)
+        ctx.geom = ((b, 1, c, H, W), ps, nk, ntok, dim, prec, m.pos_embedding_type, m.mlp_head[0].eps, depths)
         ctx.aprecs = (aprec, bprec)
         ctx.consts = consts
         ctx.drops = (d_lay, d_emb)
@@ -820,11 +666,11 @@ class TokenPoseFunction(torch.autograd.Function):
     def backward(ctx, dout):
         from . import hip_ops as ops
 
-        b, c, H, W, ps, nk, n, ntok, dim, prec, pe_type, eps_head, depths = ctx.geom
+        video_shape, ps, nk, ntok, dim, prec, pe_type, eps_head, depths = ctx.geom
+        b = video_shape[0]
         aprec, bprec = ctx.aprecs
         if aprec != 0 and bprec == 0:
             raise _lib.HiddenPoseHipError(FP32_BACKWARD_AFTER_16BIT_FORWARD.format("TokenPose"))
-        L = _lib.lib()
         allt = ctx.saved_tensors
         saved = allt[:ctx.nsaved]
         tok, cat, y = allt[ctx.nsaved:ctx.nsaved + 3]
@@ -864,11 +710,7 @@ class TokenPoseFunction(torch.autograd.Function):
             grads[2] = _joint_sum(dx, nk)
         if pe_type == "learnable" and ctx.needs_input_grad[6 + 3]:
             grads[3] = _joint_sum(dx, ntok)
-        demb = dx[:, nk:].contiguous().view(b * n, dim)
-        need_feat = ctx.needs_input_grad[0]
-        dtok, grads[0], grads[1] = linear_backward(tok, demb, params[0], need_dx=need_feat)
-        dfeat = None
-        if need_feat:
-            dfeat = torch.empty(b, c, H, W, dtype=torch.float32, device=dev)
-            _lib.check(L.hp_sformer_unpatchify(dtok.data_ptr(), dfeat.data_ptr(), b, 1, c, H, W, ps, _st(dout)), "hp_sformer_unpatchify")
+        dfeat, grads[0], grads[1] = embed_tokens_backward(dx, tok, params[0], nk, video_shape, ps, ctx.needs_input_grad[0])
+        if dfeat is not None:
+            dfeat = dfeat.view(b, *video_shape[2:])     # the feature map went through as one frame
         return (dfeat, None, None, None, None, None, *grads)

@@ -33,7 +33,6 @@ from torch import nn
 from . import _lib
 from . import _xformer as X
 from . import _xformer_autograd as _xa
-from . import hip_ops as ops
 
 
 class _Residual(nn.Module):
@@ -79,8 +78,7 @@ class Transformer(nn.Module):
         x = x.clone()
         for idx, (attn, ff) in enumerate(self.layers):
             if idx > 0 and self.all_attn:
-                patches = x[:, self.num_keypoints:]
-                patches.copy_(ops.add(patches.contiguous(), pos.expand(b, -1, -1).contiguous()))
+                X.add_position_embedding(x, pos, self.num_keypoints, "sine-full")
             a = attn.fn.fn
             dh = dim // a.heads
             h = X.layernorm(x.view(rows, dim), attn.fn.norm)
@@ -157,12 +155,8 @@ class TokenPose_L_base(nn.Module):
         if not feature.is_cuda:
             raise _lib.HiddenPoseHipError("TokenPose.forward needs a tensor on a HIP device; there is no CPU path")
         params = _xa.tokenpose_params(self)
-        drop = _xa.active_dropout(self, self.dropout, self.emb_dropout)
-        if drop is not None or (torch.is_grad_enabled() and (self.training or feature.requires_grad)
-                                and (feature.requires_grad or any(p.requires_grad for p in params))):
-            if drop is None and (self.dropout_seed is None or self.training) and (self.dropout > 0 or self.emb_dropout > 0):
-                raise _lib.HiddenPoseHipError("TokenPose training: dropout is not built without a seed (dropout / emb_dropout must "
-                                              "be 0; set dropout_seed to enable)")
+        graph, drop = _xa.training_gate(self, feature, params, self.dropout, self.emb_dropout, "TokenPose", "dropout", "emb_dropout")
+        if graph:
             aprec, bprec = X.attention_precisions(self, self.dim_head, training=True)
             with torch.cuda.device(feature.device):
                 out = _xa.TokenPoseFunction.apply(feature.contiguous().float(), self, X.PREC[self.linear_precision], aprec, bprec,
@@ -181,17 +175,10 @@ class TokenPose_L_base(nn.Module):
         aprec, _ = X.attention_precisions(self, self.dim_head, training=False)
         dev = feature.device
         with torch.cuda.device(dev):
-            tok = X.patchify(feature.view(b, 1, c, H, W), self.patch_size[0])
-            emb = X.linear(tok, self.patch_to_embedding.weight, self.patch_to_embedding.bias).view(b, -1, dim)
-            n = emb.shape[1]
-            x = torch.empty(b, nk + n, dim, dtype=torch.float32, device=dev)
-            x[:, :nk] = self.keypoint_token
-            if self.pos_embedding_type in ("sine", "sine-full"):
-                x[:, nk:] = ops.add(emb.contiguous(), self.pos_embedding[:, :n].expand(b, -1, -1).contiguous())
-            else:
-                x[:, nk:] = emb
-                x = ops.add(x, self.pos_embedding[:, :n + nk].expand(b, -1, -1).contiguous())
             pos = self.pos_embedding
+            _, x = X.embed_tokens(feature.view(b, 1, c, H, W), self.patch_size[0], self.patch_to_embedding.weight,
+                                  self.patch_to_embedding.bias, self.keypoint_token)
+            x = X.add_position_embedding(x, pos, nk, self.pos_embedding_type)
             x1 = self.transformer1.run(x, pos, prec, aprec)
             x2 = self.transformer2.run(x1, pos, prec, aprec)
             x3 = self.transformer3.run(x2, pos, prec, aprec)

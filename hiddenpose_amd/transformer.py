@@ -133,12 +133,9 @@ class TimeSformer(nn.Module):
             ps = self.patch_size
             masks = self._key_masks(mask, video, (video.shape[-2] // ps) * (video.shape[-1] // ps))
         params = _xa.timesformer_params(self)
-        drop = _xa.active_dropout(self, self.attn_dropout, self.ff_dropout)
-        if drop is not None or (torch.is_grad_enabled() and (self.training or video.requires_grad)
-                                and (video.requires_grad or any(p.requires_grad for p in params))):
-            if drop is None and (self.dropout_seed is None or self.training) and (self.attn_dropout > 0 or self.ff_dropout > 0):
-                raise _lib.HiddenPoseHipError("TimeSformer training: dropout is not built without a seed (attn_dropout / ff_dropout "
-                                              "must be 0; set dropout_seed to enable)")
+        graph, drop = _xa.training_gate(self, video, params, self.attn_dropout, self.ff_dropout, "TimeSformer", "attn_dropout",
+                                        "ff_dropout")
+        if graph:
             aprec, bprec = X.attention_precisions(self, self.dim_head, training=True)
             with torch.cuda.device(video.device):
                 out = _xa.TimeSformerFunction.apply(video.contiguous().float(), self, X.PREC[self.linear_precision], aprec, bprec,
@@ -155,16 +152,12 @@ class TimeSformer(nn.Module):
         ps, heads, dh = self.patch_size, self.heads, self.dim_head
         hp, wp = H // ps, W // ps
         n = hp * wp
-        ntok = 1 + f * n
-        dim = self.cls_token.shape[-1]
         prec = X.PREC[self.linear_precision]
         aprec, _ = X.attention_precisions(self, dh, training=False)
         dev = video.device
         with torch.cuda.device(dev):
-            emb = X.linear(X.patchify(video, ps), self.to_patch_embedding.weight, self.to_patch_embedding.bias)
-            x = torch.empty(b, ntok, dim, dtype=torch.float32, device=dev)
-            x[:, :1] = self.cls_token
-            x[:, 1:] = emb.view(b, f * n, dim)
+            _, x = X.embed_tokens(video, ps, self.to_patch_embedding.weight, self.to_patch_embedding.bias, self.cls_token)
+            ntok, dim = x.shape[1:]
             sin_s, cos_s = self.image_rot_emb.tables(hp, wp, dev)
             sin_t, cos_t = self._frame_tables(f, dev)
             rows = b * ntok
@@ -175,15 +168,9 @@ class TimeSformer(nn.Module):
                 h = X.layernorm(x.view(rows, dim), time_attn.norm).view(b, ntok, dim)
                 if self.shift_tokens:
                     h = _token_shift(h, f)
-                hperm = torch.empty_like(h)
-                hperm[:, :1] = h[:, :1]
-                hperm[:, 1:] = h[:, 1:].view(b, f, n, dim).transpose(1, 2).reshape(b, n * f, dim)
-                att = X.attention(hperm.view(rows, dim), a.to_qkv, b, ntok, heads, dh, 1, f, n, a.scale, sin_t, cos_t, prec,
+                att = X.attention(X.time_perm(h, f, n).view(rows, dim), a.to_qkv, b, ntok, heads, dh, 1, f, n, a.scale, sin_t, cos_t, prec,
                                   key_mask=mask_time, mask_patch_queries=True)
-                back = torch.empty_like(att)
-                back[:, :1] = att[:, :1]
-                back[:, 1:] = att[:, 1:].view(b, n, f, heads * dh).transpose(1, 2).reshape(b, f * n, heads * dh)
-                X.linear(back.view(rows, heads * dh), a.to_out[0].weight, a.to_out[0].bias, prec, residual=x.view(rows, dim))
+                X.linear(X.time_unperm(att, f, n).view(rows, heads * dh), a.to_out[0].weight, a.to_out[0].bias, prec, residual=x.view(rows, dim))
                 # ---- spatial attention: groups = the n patches of one frame
                 a = unwrap(spatial_attn.fn)
                 h = X.layernorm(x.view(rows, dim), spatial_attn.norm).view(b, ntok, dim)

@@ -43,6 +43,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from hiddenpose_amd import _lib  # noqa: E402
+from hiddenpose_amd import _xformer as xf  # noqa: E402
 from hiddenpose_amd import _xformer_autograd as xa  # noqa: E402
 from hiddenpose_amd import testing as hpt  # noqa: E402
 from hiddenpose_amd.tokenpose import TokenPose_L_base  # noqa: E402
@@ -142,7 +143,7 @@ def time_attention_ab(m, B, calls):
     sin_t, cos_t = m._frame_tables(f, x.device)
     with torch.no_grad():
         _, sv = xa.prenorm_attention_forward(x, p, time_attn.norm.eps, time_attn.fn.scale, heads, dh, 1, f, n, sin_t, cos_t, 0,
-                                             perm=lambda t: xa.time_perm(t, f, n), unperm=lambda t: xa.time_unperm(t, f, n))
+                                             perm=lambda t: xf.time_perm(t, f, n), unperm=lambda t: xf.time_unperm(t, f, n))
     _x, _h, q, k, k0, v, att, lse, _ab = sv
     datt = torch.randn(B, ntok, heads * dh, generator=g).cuda()
     res = {}
