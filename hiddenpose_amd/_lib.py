@@ -172,6 +172,15 @@ SIGNATURES = {
     "hp_optim_adam_multi": (_i, [_vp, _i, _d, _d, _d, _d, _vp, _sz, _vp]),
     "hp_optim_sgd_multi_workspace_bytes": (_sz, [_i]),
     "hp_optim_sgd_multi": (_i, [_vp, _i, _d, _d, _d, _d, _i, _vp, _sz, _vp]),
+    "hp_joint_heatmaps": (_i, [_fp, _fp, _i, _i, _i, _d, _d, _fp, _fp, _vp]),
+    "hp_joints_mse_workspace_bytes": (_sz, [_i, _i]),
+    "hp_joints_mse_forward": (_i, [_fp, _fp, _i, _i, _i, _i, _d, _i, _fp, _fp, _vp, _sz, _vp]),
+    "hp_joints_mse_backward": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _d, _i, _fp, _vp]),
+    "hp_simdr_loss_workspace_bytes": (_sz, [_i, _i]),
+    "hp_simdr_loss_forward": (_i, [_fp, _i, C.c_long, _fp, _i, C.c_long, _fp, _i, C.c_long, _fp, _fp, _i, _i, _d, _fp, _fp, _vp, _sz,
+                                   _vp]),
+    "hp_simdr_loss_backward": (_i, [_fp, _i, C.c_long, _fp, _i, C.c_long, _fp, _i, C.c_long, _fp, _fp, _i, _i, _d, _fp, _fp, _fp, _fp,
+                                    _fp, _vp]),
 }
 
 

@@ -76,11 +76,14 @@ def get_cfg_defaults() -> CfgNode:
         DCONV_PRECISION="auto",
     )
     c.DATASET = CfgNode(NAME="NlosPoseDataset", NUM_JOINTS=24, HEATMAP_SIZE=[64, 64, 64], VOL_SIZE=[256, 256, 256],
-                        DAWNSAMPLE_CNT=1, PHASE="train", TRAIN_PATH="", TEST_PATH="")
+                        DAWNSAMPLE_CNT=1, PHASE="train", TRAIN_PATH="", TEST_PATH="",
+                        # heat-map targets of the transformer heads (criterion.JointsMSELoss / JointTarget)
+                        TARGET_TYPE="gaussian", SIGMA=2, USE_DIFFERENT_JOINTS_WEIGHT=True,
+                        IMAGE_SIZE=[64, 64, 128])   # JointTarget: sigma' = SIGMA * HEATMAP_SIZE[0] // IMAGE_SIZE[0]
     c.TRAIN = CfgNode(OPTIMIZER="adam", LR=0.001, LR_FACTOR=0.2, LR_STEP=[2, 4, 13], BATCH_SIZE=2,
                       BEGIN_EPOCH=0, END_EPOCH=15)
     c.TEST = CfgNode(TYPE="pose_v2", BATCH_SIZE=2)
-    c.LOSS = CfgNode(TYPE="L2JointLocationLoss")
+    c.LOSS = CfgNode(TYPE="L2JointLocationLoss", LABEL_SMOOTHING=0.2, USE_TARGET_WEIGHT=False)
     c.RESULT = CfgNode(FINAL_OUTPUT_DIR="./checkpoints")
     return c
 

@@ -1361,6 +1361,142 @@ def weighted_mse(pred, gt, weights, size_average=True):
     return _WeightedMse.apply(pred, gt, weights, (1.0 / len(pred)) if size_average else 1.0)
 
 
+# ---------------------------------------------------------------- losses of the transformer heads
+def _joints_on(joints, dev):
+    """(..., >= 2) joint coordinates from the host or the device -> contiguous (R, 2) float32 on `dev`."""
+    j = torch.as_tensor(joints)
+    return j[..., :2].to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
+
+
+def joint_heatmaps(joints, H, W, sigma, tmp_size, vis=None):
+    """Gaussian target maps of R joints (utils/criterion.py:285-345, JointTarget.generate_target) -> target (R, H, W) and
+    flags (R): `vis` (or 1) where any part of the truncated Gaussian is in range, else 0; maps with a flag <= 0.5 are zero."""
+    _need_cuda(joints, "joint_heatmaps")
+    with torch.no_grad():
+        j = _joints_on(joints, joints.device)
+        R = j.shape[0]
+        v = None if vis is None else torch.as_tensor(vis).to(device=j.device, dtype=torch.float32).reshape(-1).contiguous()
+        assert v is None or v.numel() == R
+        target = torch.empty(R, H, W, dtype=torch.float32, device=j.device)
+        flags = torch.empty(R, dtype=torch.float32, device=j.device)
+        with torch.cuda.device(j.device):
+            _lib.check(_lib.lib().hp_joint_heatmaps(j.data_ptr(), _lib.ptr(v), R, H, W, float(sigma), float(tmp_size),
+                                                    target.data_ptr(), flags.data_ptr(), _stream(j)), "hp_joint_heatmaps")
+    return target, flags
+
+
+class _JointsMse(torch.autograd.Function):
+    """0.5 / (B J H W) * sum (w (pred - gaussian(joints)))^2 (utils/criterion.py:241-270) -> (loss, flags (B, J))."""
+
+    @staticmethod
+    def forward(ctx, pred, joints, sigma, use_target_weight):
+        _need_cuda(pred, "joints_mse")
+        assert pred.dim() == 4, "joints_mse: pred is (B, J, H, W)"
+        pred = pred.contiguous().float()
+        B, J, H, W = pred.shape
+        j = _joints_on(joints, pred.device)
+        assert j.shape[0] == B * J, "joints_mse: target is (B, J, >= 2)"
+        L = _lib.lib()
+        flags = torch.empty(B, J, dtype=torch.float32, device=pred.device)
+        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+        nbytes = L.hp_joints_mse_workspace_bytes(B, J)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=pred.device)
+        with torch.cuda.device(pred.device):
+            _lib.check(L.hp_joints_mse_forward(pred.data_ptr(), j.data_ptr(), B, J, H, W, float(sigma), int(bool(use_target_weight)),
+                                               flags.data_ptr(), loss.data_ptr(), ws.data_ptr(), nbytes, _stream(pred)),
+                       "hp_joints_mse_forward")
+        ctx.save_for_backward(pred, j, flags)
+        ctx.hyper = (float(sigma), int(bool(use_target_weight)))
+        ctx.mark_non_differentiable(flags)
+        return loss.reshape(()), flags
+
+    @staticmethod
+    def backward(ctx, gl, _gflags):
+        pred, j, flags = ctx.saved_tensors
+        B, J, H, W = pred.shape
+        d = torch.empty_like(pred)
+        gl = gl.reshape(1).contiguous().float()
+        with torch.cuda.device(pred.device):
+            _lib.check(_lib.lib().hp_joints_mse_backward(pred.data_ptr(), j.data_ptr(), flags.data_ptr(), gl.data_ptr(), B, J, H, W,
+                                                         ctx.hyper[0], ctx.hyper[1], d.data_ptr(), _stream(pred)),
+                       "hp_joints_mse_backward")
+        return d, None, None, None
+
+
+def joints_mse(pred, joints, sigma, use_target_weight=False):
+    """pred (B, J, H, W), joints (B, J, >= 2) on the host or the device -> (loss, flags (B, J))."""
+    return _JointsMse.apply(pred, joints, sigma, use_target_weight)
+
+
+def _simdr_rows(t, B, J):
+    """(B, J, n) prediction -> (tensor, row stride) addressable as B * J rows a constant stride apart, bins contiguous; a
+    view out[:, :, a, :] of a packed (B, J, 3, n) tensor passes unchanged, anything else is made contiguous."""
+    assert t.dim() == 3 and t.shape[0] == B and t.shape[1] == J, "simdr_loss: a prediction is (B, J, bins)"
+    if t.dtype != torch.float32:
+        t = t.float()
+    n = t.shape[2]
+    ok = t.stride(2) == 1 and t.stride(1) >= n and (B == 1 or t.stride(0) == J * t.stride(1))
+    if not ok:
+        t = t.contiguous()
+    return t, (t.stride(1) if J > 1 or B == 1 else t.stride(0))
+
+
+class _SimdrLoss(torch.autograd.Function):
+    """Label-smoothed KL over the log-softmax of three coordinate classifiers (utils/criterion.py:29-63)."""
+
+    @staticmethod
+    def forward(ctx, ox, oy, oz, target, weight, ls):
+        _need_cuda(ox, "simdr_loss")
+        B, J = ox.shape[0], ox.shape[1]
+        dev = ox.device
+        (ox, sx), (oy, sy), (oz, sz) = (_simdr_rows(t, B, J) for t in (ox, oy, oz))
+        tg = torch.as_tensor(target).to(device=dev, dtype=torch.float32).reshape(B * J, -1)[:, :3].contiguous()
+        assert tg.shape[1] == 3, "simdr_loss: target is (B, J, 3)"
+        w = None if weight is None else torch.as_tensor(weight).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert w is None or w.numel() == B * J, "simdr_loss: weight is (B, J) or (B, J, 1)"
+        L = _lib.lib()
+        stat = torch.empty(B * J * 3 * 2, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        nbytes = L.hp_simdr_loss_workspace_bytes(B, J)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.hp_simdr_loss_forward(ox.data_ptr(), ox.shape[2], sx, oy.data_ptr(), oy.shape[2], sy, oz.data_ptr(),
+                                               oz.shape[2], sz, tg.data_ptr(), _lib.ptr(w), B, J, float(ls), stat.data_ptr(),
+                                               loss.data_ptr(), ws.data_ptr(), nbytes, _stream(ox)), "hp_simdr_loss_forward")
+        ctx.save_for_backward(ox, oy, oz, tg, stat, *(() if w is None else (w,)))
+        ctx.hyper = (B, J, float(ls), sx, sy, sz)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        ox, oy, oz, tg, stat, *rest = ctx.saved_tensors
+        w = rest[0] if rest else None
+        B, J, ls, sx, sy, sz = ctx.hyper
+        # gradients with the strides of the predictions: a packed (B, J, 3, n) input gets three views of one packed buffer
+        n = ox.shape[2]
+        if (ox.shape == oy.shape == oz.shape and sx == sy == sz == 3 * n and oy.data_ptr() - ox.data_ptr() == 4 * n
+                and oz.data_ptr() - oy.data_ptr() == 4 * n):
+            packed = torch.empty(B, J, 3, n, dtype=torch.float32, device=ox.device)
+            ds = [packed[:, :, a, :] for a in range(3)]
+        else:
+            if not (ox.is_contiguous() and oy.is_contiguous() and oz.is_contiguous()):   # other strided rows: dense copies
+                ox, oy, oz = ox.contiguous(), oy.contiguous(), oz.contiguous()
+                sx, sy, sz = ox.shape[2], oy.shape[2], oz.shape[2]
+            ds = [torch.empty_like(t) for t in (ox, oy, oz)]
+        gl = gl.reshape(1).contiguous().float()
+        with torch.cuda.device(ox.device):
+            _lib.check(_lib.lib().hp_simdr_loss_backward(ox.data_ptr(), ox.shape[2], sx, oy.data_ptr(), oy.shape[2], sy, oz.data_ptr(),
+                                                         oz.shape[2], sz, tg.data_ptr(), _lib.ptr(w), B, J, ls, stat.data_ptr(),
+                                                         gl.data_ptr(), ds[0].data_ptr(), ds[1].data_ptr(), ds[2].data_ptr(),
+                                                         _stream(ox)), "hp_simdr_loss_backward")
+        return ds[0], ds[1], ds[2], None, None, None
+
+
+def simdr_loss(output_x, output_y, output_z, target, target_weight=None, label_smoothing=0.2):
+    """(B, J, n_x / n_y / n_z) classifier logits, target (B, J, 3), weight (B, J), (B, J, 1) or None -> the scalar loss."""
+    return _SimdrLoss.apply(output_x, output_y, output_z, target, target_weight, label_smoothing)
+
+
 def visible_projection(x):
     """VisibleNet.forward (models/feature_propagation.py:296-312): relu -> per-volume min-max normalisation -> x 1e5 ->
     the 4 largest values along depth and their depth coordinates, concatenated on the channel axis:

@@ -701,6 +701,57 @@ int hp_optim_sgd_multi(const hp_optim_sgd_rec* recs, int count, double lr, doubl
                        double weight_decay, int nesterov, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Losses of the transformer heads: the Gaussian heat-map MSE TokenPose-L trains on (utils/criterion.py:166-270,
+ * JointsMSELoss; :273-345, JointTarget) and the label-smoothed KL loss of the 1-D coordinate classifiers ("SimDR", :10-63,
+ * NMTNORMCritierion).  Every tensor is contiguous fp32 on the device unless a stride is named; pointers need 4-byte
+ * alignment only (16-byte accesses are used where a map's base allows them).  Both losses are summed without atomics, in a
+ * fixed order in double: a loss is bit-reproducible from call to call.  Every check comes before any launch.
+ *
+ * Heat-map.  joints (R, 2) holds (mu_x, mu_y) in heat-map pixels, x along W; a map is (H, W).  Range flag of a joint, in
+ * float32 with truncation toward zero (Python's int()): ul = trunc(mu - t), br = trunc(mu + t + 1);
+ * flag = 0 if ul.x >= W or ul.y >= H or br.x < 0 or br.y < 0, else 1.  Target value g[y, x] =
+ * exp(-((x - mu_x)^2 + (y - mu_y)^2) / (2 sigma^2)) where the flag is set, 0 elsewhere; the kernels build it as a product
+ * of two 1-D tables and never store it (the backward builds it again).
+ *   hp_joint_heatmaps        renders the maps of R joints into target (R, H, W), t = tmp_size (JointTarget: 3 sigma').  vis
+ *                            (R) may be NULL; otherwise flags[r] = vis[r] where the joint is in range, 0 elsewhere, and a map
+ *                            is drawn where flags[r] > 0.5 (JointTarget.generate_target).
+ *   hp_joints_mse_forward    loss = 0.5 / (B J H W) * sum (w_bj (pred - g))^2, t = sigma; w_bj = 1, or the flag with
+ *                            use_target_weight (out-of-range joints are compared against zeros without it).  flags (B J) is
+ *                            written; workspace: hp_joints_mse_workspace_bytes(B, J) bytes of device memory.
+ *   hp_joints_mse_backward   dpred = gloss[0] * w_bj^2 (pred - g) / (B J H W) from the forward's flags; gloss is a device scalar.
+ * HP_ERR_BAD_ARG: a null pointer, B, J, H or W < 1, sigma not positive and finite, more than 2^31 - 1 maps or H * W beyond
+ * the 32-bit index of a map, a null or too small workspace.  HP_ERR_UNSUPPORTED: H + W > 15360 (the tables live in LDS).
+ *
+ * SimDR.  Three predictions (B J rows of n_a bins, consecutive rows stride_a elements apart, bins contiguous: views
+ * out[:, :, a, :] of one packed (B, J, 3, n) tensor need no copy), target (B J, 3) coordinates, weight (B J) or NULL (ones).
+ * Per row and axis: s = log_softmax(row); label = trunc(target); t_k = ls / (n_a - 1), t_label = 1 - ls;
+ * row loss = (1 / n_a) sum_k t_k (log t_k - s_k) with 0 log 0 = 0 (ls = 0: -s_label / n_a);
+ * loss = 1 / (J B) * sum over rows and axes of weight * row loss.  The label is only compared with k, never used as an index:
+ * with a label outside [0, n_a) no bin holds the confidence and nothing is read or written out of bounds.
+ *   hp_simdr_loss_forward    writes loss and stat (B J 3 pairs: row maximum, log of the sum of exp(x - maximum)) for the backward;
+ *                            workspace: hp_simdr_loss_workspace_bytes(B, J) bytes.
+ *   hp_simdr_loss_backward   d_a[k] = gloss[0] * (softmax_k T - t_k) weight / (J B n_a), T = sum_k t_k, into dx / dy / dz with
+ *                            the strides of the predictions.
+ * HP_ERR_BAD_ARG: a null pointer (weight excepted), B or J < 1, an axis with fewer than 2 bins, a stride shorter than its
+ * row, label_smoothing outside [0, 1) or not finite, more than (2^31 - 1) / 3 rows, a null or too small workspace.
+ * ---------------------------------------------------------------------- */
+int hp_joint_heatmaps(const float* joints, const float* vis, int R, int H, int W, double sigma, double tmp_size, float* target,
+                      float* flags, void* stream);
+size_t hp_joints_mse_workspace_bytes(int B, int J);
+int hp_joints_mse_forward(const float* pred, const float* joints, int B, int J, int H, int W, double sigma, int use_target_weight,
+                          float* flags, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int hp_joints_mse_backward(const float* pred, const float* joints, const float* flags, const float* gloss, int B, int J, int H,
+                           int W, double sigma, int use_target_weight, float* dpred, void* stream);
+size_t hp_simdr_loss_workspace_bytes(int B, int J);
+int hp_simdr_loss_forward(const float* pred_x, int nx, long stride_x, const float* pred_y, int ny, long stride_y,
+                          const float* pred_z, int nz, long stride_z, const float* target, const float* weight, int B, int J,
+                          double label_smoothing, float* stat, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int hp_simdr_loss_backward(const float* pred_x, int nx, long stride_x, const float* pred_y, int ny, long stride_y,
+                           const float* pred_z, int nz, long stride_z, const float* target, const float* weight, int B, int J,
+                           double label_smoothing, const float* stat, const float* gloss, float* dx, float* dy, float* dz,
+                           void* stream);
+
+/* ------------------------------------------------------------------------
  * Measurement ingest (utils/nlos_pose_dataloader.py:71-144, utils/loadrealdata.py:6-15): the per-sample
  * CPU work of the reference's Dataset.__getitem__, moved to the device.
  * ---------------------------------------------------------------------- */
