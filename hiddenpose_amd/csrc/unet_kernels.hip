@@ -37,29 +37,57 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float* sh) {
   __syncthreads();
 }
 
+// block-wide sum of two doubles; result valid in thread 0
+__device__ __forceinline__ void block_sum2d(double& a, double& b, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o);
+    b += __shfl_xor(b, o);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    sh[wave * 2] = a;
+    sh[wave * 2 + 1] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = 0.;
+    b = 0.;
+    for (int w = 0; w < UT / 64; ++w) {
+      a += sh[w * 2];
+      b += sh[w * 2 + 1];
+    }
+  }
+  __syncthreads();
+}
+
 // ---- GroupNorm forward: per (b, channel) sum / sum of squares (fp64 atomics), then apply.
 // grid (chunks, B*C); acc[(b*C + c)*2 + {0,1}]
+// The squares and both sums are formed in double from the first add on: the variance is E[z^2] - m^2, which cancels
+// (m / std)^2 of the sums' precision, and float32 squares and block partials left y 3e-6 ... 1.3e-5 from float64 at
+// |m| / std = 8 on small planes (bar 1e-6).  Still one pass over z; the kernel is HBM-bound either way.
 __global__ __launch_bounds__(UT) void k_plane_stats(const float* __restrict__ z, double* __restrict__ acc, long V) {
-  __shared__ float sh[2 * UT / 64];
+  __shared__ double sh[2 * UT / 64];
   const long plane = blockIdx.y;
   const float4* p = (const float4*)(z + plane * V);
   const long n4 = V / 4;
-  float s = 0.f, q = 0.f;
+  double s = 0., q = 0.;
   for (long i = (long)blockIdx.x * UT + threadIdx.x; i < n4; i += (long)gridDim.x * UT) {
     const float4 v = p[i];
-    s += v.x + v.y + v.z + v.w;
-    q += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    const double x = v.x, y = v.y, zz = v.z, w = v.w;
+    s += (x + y) + (zz + w);
+    q += (x * x + y * y) + (zz * zz + w * w);
   }
   if (blockIdx.x == 0)
     for (long i = n4 * 4 + threadIdx.x; i < V; i += UT) {
-      const float v = z[plane * V + i];
+      const double v = z[plane * V + i];
       s += v;
       q += v * v;
     }
-  block_sum2(s, q, sh);
+  block_sum2d(s, q, sh);
   if (threadIdx.x == 0) {
-    atomicAdd(acc + plane * 2, (double)s);
-    atomicAdd(acc + plane * 2 + 1, (double)q);
+    atomicAdd(acc + plane * 2, s);
+    atomicAdd(acc + plane * 2 + 1, q);
   }
 }
 
@@ -673,8 +701,10 @@ extern "C" size_t hp_groupnorm_workspace_bytes(int B, int C) { return sizeof(dou
 extern "C" int hp_groupnorm_relu_forward_v2(const float* z, float* y, int B, int C, int G, long V, const float* gamma,
                                             const float* beta, float eps, const double* chan_stats, float* mean, float* rstd,
                                             float* scale, float* shift, void* workspace, void* stream) {
+  // the sizes first: C % G with G = 0 is an integer division by zero on the host, not a refusal
+  HP_REQUIRE(B > 0 && C > 0 && G > 0 && V > 0, "hp_groupnorm_relu_forward: B, C, G and V must be positive");
   HP_REQUIRE(z && y && gamma && beta && mean && rstd && scale && shift && workspace && C % G == 0,
-             "hp_groupnorm_relu_forward: bad argument");
+             "hp_groupnorm_relu_forward: bad argument (null pointer, or C is no multiple of G)");
   hipStream_t st = (hipStream_t)stream;
   double* acc = (double*)workspace;
   const dim3 grid(chunks_for(V, (long)B * C), (unsigned)(B * C));
@@ -707,8 +737,9 @@ extern "C" int hp_groupnorm_relu_forward(const float* z, float* y, int B, int C,
 extern "C" int hp_groupnorm_relu_backward_v2(const float* dy, const float* z, float* dz, int B, int C, int G, long V,
                                              const float* gamma, const float* mean, const float* rstd, const float* scale,
                                              const float* shift, float* dgamma, float* dbeta, void* workspace, void* stream) {
+  HP_REQUIRE(B > 0 && C > 0 && G > 0 && V > 0, "hp_groupnorm_relu_backward: B, C, G and V must be positive");
   HP_REQUIRE(dy && z && dz && gamma && mean && rstd && scale && shift && dgamma && dbeta && workspace && C % G == 0,
-             "hp_groupnorm_relu_backward: bad argument");
+             "hp_groupnorm_relu_backward: bad argument (null pointer, or C is no multiple of G)");
   hipStream_t st = (hipStream_t)stream;
   double* acc = (double*)workspace;
   float* ca = (float*)(acc + 2 * (long)B * C);
@@ -839,8 +870,11 @@ extern "C" int hp_upsample_trilinear2x_backward_ws(const float* dy, float* dx, i
                                                    int c_off, void* workspace, void* stream) {
   HP_REQUIRE(dy && dx && workspace && c_off >= 0 && c_off + C <= Ctot, "hp_upsample_trilinear2x_backward_ws: bad argument");
   const size_t n1 = (size_t)B * C * 2 * D * 2 * H * W, n2 = (size_t)B * C * 2 * D * H * W, n3 = (size_t)B * C * D * H * W;
-  // 32-bit element indices inside a pass, tables of 1024 positions per axis, float4 along w in the h and d passes
-  if (n1 >= (1ull << 32) || D > 1024 || H > 1024 || W > 1024 || W % 4 != 0)
+  // 32-bit element indices inside a pass, tables of 1024 positions per axis, float4 along w in the h and d passes.
+  // The passes walk an `unsigned` index with i += gridDim.x * UT (at most 2048 * 256 per trip): the largest pass (n1 items)
+  // must end a whole grid stride below 2^32, or the index of a thread in its last trip wraps to a small value that is
+  // again < n1 and the loop never ends.  Such tensors take the fused kernel, whose index is 64-bit.
+  if (n1 >= (1ull << 32) - 2048ull * UT || D > 1024 || H > 1024 || W > 1024 || W % 4 != 0)
     return hp_upsample_trilinear2x_backward(dy, dx, B, C, D, H, W, Ctot, c_off, stream);
   hipStream_t st = (hipStream_t)stream;
   HP_PROF("upsample2_bwd", st);
