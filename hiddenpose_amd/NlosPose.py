@@ -2,7 +2,8 @@
 
 Same constructor argument (a cfg node), same attribute / state_dict names and the same call contract as the
 reference's models/NlosPose.py: `NlosPose(cfg)(meas)` maps a transient volume (B,1,T,H,W) to
-(heat-maps (B,24,T/2,H/2,W/2), refined volume (B,1,T,H,W)).  Stage order (reference :49-59):
+(heat-maps (B,24,T/2,H/2,W/2), refined volume (B,1,T,H,W)); with the optional MODEL.FE_STRIDE = 2 the input is
+(B,1,2T,2H,2W) and everything after the feature extraction is unchanged.  Stage order (reference :49-59):
 feature extraction -> light-cone transform over the full time window -> per-volume normalisation to [0,10] ->
 U-Net refinement -> heat-map regression on (feature + refinement).  The LCT owns no parameters, so there is
 nothing under `feature_propagation.` in the state_dict (as in the reference).
@@ -34,7 +35,10 @@ class NlosPose(nn.Module):
             raise NotImplementedError(f"backbone {m.BACKBONE!r} is not built: the reference's own forward cannot run with it "
                                       "(models/NlosPose.py:49-59); its config selects posenet3d_50")
         self.time_begin, self.time_end = 0, m.TIME_SIZE
-        self.feature_extraction = FeatureExtraction(m.BASEDIM, m.IN_CHANNELS, stride=1)
+        # Optional MODEL.FE_STRIDE (absent = 1, the reference's NlosPose): with 2 the module halves every extent, the input is
+        # (B,1,2*TIME_SIZE,2*N,2*N) and TIME_SIZE / IMAGE_SIZE / BIN_LEN keep describing the volume the LCT sees (so BIN_LEN is
+        # the doubled bin length of the capture, as in the reference's demo, utils/nlos_dataloader.py:168-175).
+        self.feature_extraction = FeatureExtraction(m.BASEDIM, m.IN_CHANNELS, stride=getattr(m, "FE_STRIDE", 1))
         self.feature_propagation = FeaturePropagation(image_size=m.IMAGE_SIZE[0], time_size=m.TIME_SIZE,
                                                       bin_len=m.BIN_LEN, wall_size=m.WALL_SIZE, dnum=m.DNUM,
                                                       dev=cfg.DEVICE)

@@ -80,6 +80,11 @@ SIGNATURES = {
     "hp_dconv3_backward_weight_p": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "hp_dconv3_backward_weight_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "hp_dconv3_backward_weight": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "hp_fe_entry_forward": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
+    "hp_fe_entry_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "hp_fe_entry_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "hp_bcast_add_forward": (_i, [_fp, _fp, _fp, _i, _i, C.c_long, _vp]),
+    "hp_channel_sum": (_i, [_fp, _fp, _i, _i, C.c_long, _vp]),
     "hp_groupnorm_workspace_bytes": (_sz, [_i, _i]),
     "hp_groupnorm_relu_forward": (_i, [_fp, _fp, _i, _i, _i, C.c_long, _fp, _fp, C.c_float, _fp, _fp, _vp, _vp]),
     "hp_groupnorm_relu_forward_v2": (_i, [_fp, _fp, _i, _i, _i, C.c_long, _fp, _fp, C.c_float, _vp, _fp, _fp, _fp, _fp, _vp, _vp]),

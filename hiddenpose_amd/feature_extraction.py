@@ -3,7 +3,8 @@
 Drop-in for models/feature_extraction.py `FeatureExtraction` (:122-171) and
 `ResConv3D` (:228-256): same constructor, same state_dict keys
 (`weights`, `conv1.1.*`, `conv1.{2,3}.tmp.{1,4}.*`), same forward contract
-(B,1,T,H,W) -> (B,basedim,T,H,W).
+(B,1,T,H,W) -> (B,basedim,To,Ho,Wo) with To = (T - 1) // stride + 1 and likewise Ho, Wo, for stride 1 or 2 and any
+basedim >= 1.
 
 y = ResConv(ResConv(conv(reppad(x)))) + conv_zeropad(x, weights)
 """
@@ -49,5 +50,8 @@ class FeatureExtraction(nn.Module):
 
     def forward(self, x):
         if self.stride == 1 and self.conv1[1].out_channels == 1:
-            return ops.feature_extraction_fused(x, self)
-        raise NotImplementedError("FeatureExtraction: only stride 1, basedim 1 (the NlosPose configuration) is built")
+            return ops.feature_extraction_fused(x, self)   # the NlosPose configuration: box branch in the last epilogue
+        if self.stride in (1, 2):
+            return ops.feature_extraction_strided(x, self)   # strided two-branch entry kernel + broadcast join
+        raise NotImplementedError(f"FeatureExtraction: stride {self.stride!r} is not built; supported: stride 1 or 2 with "
+                                  "any basedim >= 1")

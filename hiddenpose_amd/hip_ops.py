@@ -271,7 +271,7 @@ class _ConvGnRelu(torch.autograd.Function):
 # ---------------------------------------------------------------- FeatureExtraction (rows A1, A2)
 def conv3d_reppad(x, w, b, stride=1, residual=None, slope=1.0):
     """ReplicationPad3d(1) + Conv3d(3^3) [+ residual] [+ LeakyReLU(slope)] in one kernel."""
-    assert stride == 1, "NlosPose uses FeatureExtraction with stride 1 (models/NlosPose.py:20-24)"
+    assert stride == 1, "same-size convolution only; the strided entry of FeatureExtraction is `fe_entry`"
     _note_use(w)
     return _DConv3.apply(x, w, b, True, residual, slope)
 
@@ -320,6 +320,96 @@ def feature_extraction_fused(x, fe):
     a = fe.conv1[3](fe.conv1[2](a))
     _note_use(fe.weights)
     return _DConv3.apply(x, fe.weights, None, False, a, 1.0)   # box filter branch + learned branch, added in the epilogue
+
+
+class _FEEntry(torch.autograd.Function):
+    """(a, box) of FeatureExtraction's entry at stride 1 or 2 (csrc/fe_entry_kernels.hip, hp_fe_entry_*): one pass over
+    x (B,1,D,H,W) writes a = Conv3d(1, C, 3, stride, bias)(ReplicationPad3d(1)(x)) and the zero-padded box branch
+    box = conv3d(x, weights, stride, padding 1).  Exact fp32 whatever `set_dconv_precision` says (cin == 1); the weight
+    gradients stay on the main stream."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, weights, stride):
+        _need_cuda(x, "fe_entry")
+        L = _lib.lib()
+        x, w, weights = x.contiguous(), w.contiguous(), weights.contiguous()
+        b, cin, d, h, wd = x.shape
+        assert cin == 1, f"input channels should be 1, not {cin}"
+        c, s = w.shape[0], int(stride)
+        do, ho, wo = ((n - 1) // s + 1 if s > 0 else 0 for n in (d, h, wd))
+        a = torch.empty(b, c, do, ho, wo, dtype=torch.float32, device=x.device)
+        box = torch.empty(b, 1, do, ho, wo, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(L.hp_fe_entry_forward(x.data_ptr(), w.data_ptr(), _lib.ptr(bias), weights.data_ptr(), a.data_ptr(),
+                                             box.data_ptr(), b, c, d, h, wd, s, _stream(x)), "hp_fe_entry_forward")
+        ctx.save_for_backward(x, w, weights)
+        ctx.cfg = (s, bias is not None)
+        return a, box
+
+    @staticmethod
+    def backward(ctx, ga, gbox):
+        L = _lib.lib()
+        x, w, weights = ctx.saved_tensors
+        s, has_bias = ctx.cfg
+        b, _, d, h, wd = x.shape
+        c = w.shape[0]
+        ga, gbox = ga.contiguous(), gbox.contiguous()
+        dw = torch.empty_like(w)
+        db = torch.empty(c, dtype=torch.float32, device=x.device) if has_bias else None
+        dwb = torch.empty_like(weights)
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        nb = int(L.hp_fe_entry_backward_workspace_bytes(b, c, d, h, wd, s))
+        ws = torch.empty(nb // 4, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(L.hp_fe_entry_backward(x.data_ptr(), ga.data_ptr(), gbox.data_ptr(), w.data_ptr(), weights.data_ptr(),
+                                              dw.data_ptr(), _lib.ptr(db), dwb.data_ptr(), _lib.ptr(gx), b, c, d, h, wd, s,
+                                              ws.data_ptr(), _stream(x)), "hp_fe_entry_backward")
+        return gx, dw, db, dwb, None
+
+
+def fe_entry(x, w, bias, weights, stride):
+    return _FEEntry.apply(x, w, bias, weights, stride)
+
+
+class _BcastAdd(torch.autograd.Function):
+    """y (B,C,..) = t (B,C,..) + box (B,1,..): the join of FeatureExtraction's two branches when the box channel is
+    broadcast; backward gt = gy, gbox = sum over the channels in index order (hp_bcast_add_forward / hp_channel_sum)."""
+
+    @staticmethod
+    def forward(ctx, t, box):
+        _need_cuda(t, "bcast_add")
+        t, box = t.contiguous(), box.contiguous()
+        b, c = t.shape[:2]
+        assert box.shape == (b, 1) + tuple(t.shape[2:]), f"bcast_add: box {tuple(box.shape)} does not match t {tuple(t.shape)}"
+        y = torch.empty_like(t)
+        with torch.cuda.device(t.device):
+            _lib.check(_lib.lib().hp_bcast_add_forward(t.data_ptr(), box.data_ptr(), y.data_ptr(), b, c, t.numel() // (b * c),
+                                                       _stream(t)), "hp_bcast_add_forward")
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        gt = gy if ctx.needs_input_grad[0] else None
+        gbox = None
+        if ctx.needs_input_grad[1]:
+            gy = gy.contiguous()
+            b, c = gy.shape[:2]
+            gbox = torch.empty((b, 1) + tuple(gy.shape[2:]), dtype=torch.float32, device=gy.device)
+            with torch.cuda.device(gy.device):
+                _lib.check(_lib.lib().hp_channel_sum(gy.data_ptr(), gbox.data_ptr(), b, c, gy.numel() // (b * c), _stream(gy)),
+                           "hp_channel_sum")
+        return gt, gbox
+
+
+def bcast_add(t, box):
+    return _BcastAdd.apply(t, box)
+
+
+def feature_extraction_strided(x, fe):
+    """FeatureExtraction at every (stride in {1, 2}, basedim >= 1) but (1, 1), which keeps `feature_extraction_fused`."""
+    _need_cuda(x, "feature_extraction")
+    a, box = fe_entry(x, fe.conv1[1].weight, fe.conv1[1].bias, fe.weights, fe.stride)
+    return bcast_add(fe.conv1[3](fe.conv1[2](a)), box)
 
 
 # ---------------------------------------------------------------- normalize_feature (row C8)

@@ -320,6 +320,35 @@ int hp_dconv3_backward_weight(const float* x, const float* gy, float* dw, float*
                               int H, int W, int replicate_pad, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Entry of FeatureExtraction at stride 1 or 2 and any channel count C >= 1 (models/feature_extraction.py:122-171: the
+ * constructor's default stride is 2, :132; models/NlosPose.py:51 "(2,1,128,64,64) -> (2,2,64,32,32)").  Planar fp32.
+ * One kernel reads x (B,1,D,H,W) once and writes both branches of the module's forward (:160-171):
+ *   a   (B,C,Do,Ho,Wo) = Conv3d(1, C, 3, stride, bias)(ReplicationPad3d(1)(x))        (:147-155; w (C,1,3,3,3), bias (C) or NULL)
+ *   box (B,1,Do,Ho,Wo) = conv3d(x, box_w (1,1,3,3,3), stride, padding 1), zero padding (:167)
+ * with Do = (D - 1) / stride + 1 (integer division), likewise Ho and Wo.  cin == 1, so these kernels run exact fp32
+ * whatever precision the thin-channel convolutions above are asked for (the rule of their 1 -> 1 layers).
+ * Arguments are checked before any device call; HP_ERR_BAD_ARG: stride outside {1, 2}, C < 1, a non-positive extent, a
+ * sample of 2^29 voxels or more, a null required pointer (bias, dbias and gx are the optional ones).
+ * ---------------------------------------------------------------------- */
+int hp_fe_entry_forward(const float* x, const float* w, const float* bias, const float* box_w, float* a, float* box, int B,
+                        int C, int D, int H, int W, int stride, void* stream);
+/* Backward of the above from ga = dL/da and gbox = dL/dbox: dw (C,1,3,3,3), dbias (C, may be NULL), dbox_w (1,1,3,3,3) are
+ * overwritten with sums of per-workgroup partial records (workspace, device, sized by the query; 0 for arguments the call
+ * would refuse) added in a fixed order: no float atomics, two runs are bit-identical.  gx (B,1,D,H,W), when not NULL, is
+ * the adjoint of both branches in one pass over the output-sized gradients; the replicate-padded branch folds the taps
+ * that pointed outside the volume onto the border voxel (position -1 onto 0; position n onto n - 1, which at stride 2 is
+ * read only when n is odd).  A NULL gx skips it. */
+size_t hp_fe_entry_backward_workspace_bytes(int B, int C, int D, int H, int W, int stride);
+int hp_fe_entry_backward(const float* x, const float* ga, const float* gbox, const float* w, const float* box_w, float* dw,
+                         float* dbias, float* dbox_w, float* gx, int B, int C, int D, int H, int W, int stride,
+                         void* workspace, void* stream);
+/* The join of the two branches (feature_extraction.py:170, `x_conv1 + x_conv2` broadcasting the single box channel) and its
+ * adjoint, over output-sized tensors: y (B,C,V) = t (B,C,V) + box (B,1,V);  gbox (B,1,V) = sum over c of gy (B,C,V), the
+ * channels added in index order (dL/dt is gy itself).  B * C < 65536. */
+int hp_bcast_add_forward(const float* t, const float* box, float* y, int B, int C, long V, void* stream);
+int hp_channel_sum(const float* gy, float* gbox, int B, int C, long V, void* stream);
+
+/* ------------------------------------------------------------------------
  * UNet3d memory-bound stages (unet/unet3d.py), planar (B, C, D, H, W) fp32; V = D*H*W.
  * ---------------------------------------------------------------------- */
 size_t hp_groupnorm_workspace_bytes(int B, int C);
