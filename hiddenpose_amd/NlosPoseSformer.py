@@ -15,6 +15,16 @@ adds 1 to `dropout_step` (also under torch.no_grad(), as torch's dropout follows
 of the state_dict.  With `dropout_seed` None nothing changes: a training forward with a probability > 0 is refused, the
 no-grad path ignores dropout.  In eval mode nothing is drawn, with or without a seed.  Sites per layer: the spatial attention's
 to_out (attn_dropout), then the feed-forward's hidden activation after the GEGLU (ff_dropout).
+
+`rotary_emb=False` (:55-60, :113-119) is the learned-position variant: the module owns `pose_emb = nn.Embedding(num_frames *
+num_patches + 1, dim)` (the reference's spelling, default initialisation; the checkpoint key is `pose_emb.weight`) and neither
+rotary module.  The table's first ntok rows are added to the token matrix, joint tokens included, once before the first layer,
+in the pass that assembles [joints | patch embedding] (hp_tokens_assemble_forward / _backward); every attention
+then runs without rotation (rot_dim 0: the joint queries see K0 = K), at every attention precision.  The table has
+num_frames * num_patches + 1 rows and the joint tokens take num_joints of them, so a clip fits only while num_joints + f n <=
+num_frames n + 1: a longer one (a full clip, with the default 24 joints) raises IndexError before anything is launched, as the
+reference's lookup does.  A shorter clip uses the table's prefix and leaves an exactly zero gradient in the rows behind it.
+The precisions and dropout compose with it unchanged (the table add is not a dropout site); a frozen table gets no gradient.
 """
 from __future__ import annotations
 
@@ -90,7 +100,6 @@ class NlosPoseSformer(nn.Module):
                  dim_head=64, attn_dropout=0.0, ff_dropout=0.0, rotary_emb=True, out_dim=64 * 2 * 3, batch_size=2):
         super().__init__()
         assert image_size % patch_size == 0, "Image dimensions must be divisible by the patch size."
-        assert rotary_emb, "only the rotary-embedding variant (config_noise.py:51) is built"
         _lib.lib()
         self.heads, self.dim_head, self.patch_size, self.num_joints = heads, dim_head, patch_size, num_joints
         self.attn_dropout, self.ff_dropout = attn_dropout, ff_dropout
@@ -99,12 +108,20 @@ class NlosPoseSformer(nn.Module):
         self.to_patch_embedding = nn.Linear(patch_dim, dim)
         self.joints_token = nn.Parameter(torch.zeros(1, num_joints, dim))
         nn.init.trunc_normal_(self.joints_token, std=0.02)
-        self.frame_rot_emb = RotaryEmbedding(dim_head)
-        self.image_rot_emb = AxialRotaryEmbedding(dim_head)
+        self.use_rotary_emb = rotary_emb
+        if rotary_emb:
+            self.frame_rot_emb = RotaryEmbedding(dim_head)
+            self.image_rot_emb = AxialRotaryEmbedding(dim_head)
+        else:   # :59-60, the reference's spelling (it is the checkpoint key)
+            self.pose_emb = nn.Embedding(num_frames * (image_size // patch_size) ** 2 + 1, dim)
         self.layers = nn.ModuleList([
             nn.ModuleList([_PreNorm(dim, _Attention(dim, dim_head, heads)), _PreNorm(dim, _Attention(dim, dim_head, heads)),
                            _PreNorm(dim, _FeedForward(dim))]) for _ in range(depth)])
         self.to_out = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, out_dim))
+
+    def position_table(self):
+        """The learned position table (num_frames * num_patches + 1, dim) of the rotary_emb=False variant, else None."""
+        return None if self.use_rotary_emb else self.pose_emb.weight
 
     def forward(self, video, mask=None):
         """An autograd graph is built when grad mode is on, the module is in training mode or `video` requires grad, and
@@ -114,6 +131,10 @@ class NlosPoseSformer(nn.Module):
         no_grad) the no-graph path runs, launch for launch as an inference-only module would.  With dropout active (module
         docstring) the forward always goes through SformerFunction, under no_grad too, and adds 1 to dropout_step."""
         assert mask is None, "frame masks are ignored by the reference's attention (:177-179) and not supported"
+        if not self.use_rotary_emb:
+            ps = self.patch_size
+            _xf.check_table_rows("NlosPoseSformer", self.pose_emb.weight, self.num_joints, video.shape[1],
+                                 (video.shape[-2] // ps) * (video.shape[-1] // ps))
         if not video.is_cuda:
             raise _lib.HiddenPoseHipError("NlosPoseSformer.forward needs a tensor on a HIP device; there is no CPU path")
         params = _xa.trainable_params(self)
@@ -142,10 +163,15 @@ class NlosPoseSformer(nn.Module):
         prec = _xf.PREC[self.linear_precision]
         aprec, _ = _xf.attention_precisions(self, dh, training=False)
         with torch.cuda.device(dev):
-            _, x = _xf.embed_tokens(video, ps, self.to_patch_embedding.weight, self.to_patch_embedding.bias, self.joints_token)
+            if self.use_rotary_emb:
+                _, x = _xf.embed_tokens(video, ps, self.to_patch_embedding.weight, self.to_patch_embedding.bias, self.joints_token)
+                sin_t, cos_t = self.image_rot_emb.tables(hp, wp, dev)
+                rot_dim = sin_t.shape[-1]
+            else:   # the learned table goes into the token matrix once; the attention then runs without rotation
+                _, x = _xf.assemble_tokens(video, ps, self.to_patch_embedding.weight, self.to_patch_embedding.bias, self.joints_token,
+                                           self.pose_emb.weight)
+                sin_t, cos_t, rot_dim = None, None, 0
             ntok, dim = x.shape[1:]
-            sin_t, cos_t = self.image_rot_emb.tables(hp, wp, dev)
-            rot_dim = sin_t.shape[-1]
             rows = b * ntok
             inner = heads * dh
             h = torch.empty_like(x)
@@ -161,7 +187,7 @@ class NlosPoseSformer(nn.Module):
                                                   spatial.norm.bias.data_ptr(), spatial.norm.eps, 0, 0, st), "hp_layernorm_forward")
                 qkv = _xf.linear(h.view(rows, dim), a.to_qkv.weight, None, prec)
                 _lib.check(L.hp_sformer_qkv_prepare(qkv.data_ptr(), q.data_ptr(), k.data_ptr(), k0.data_ptr(), v.data_ptr(), b, ntok, heads, dh,
-                                                    nj, n, a.scale, sin_t.data_ptr(), cos_t.data_ptr(), rot_dim, st),
+                                                    nj, n, a.scale, _lib.ptr(sin_t), _lib.ptr(cos_t), rot_dim, st),
                            "hp_sformer_qkv_prepare")
                 _xf.attention_forward(q, k, k0, v, att, None, b, heads, dh, ntok, nj, n, f, aws, precision=aprec)
                 _xf.linear(att.view(rows, inner), a.to_out[0].weight, a.to_out[0].bias, prec, residual=x.view(rows, dim))

@@ -173,6 +173,8 @@ SIGNATURES = {
     "hp_linear_backward_weight": (_i, [_fp, _fp, _fp, _fp, C.c_long, _i, _i, _i, _vp, _sz, _vp]),
     "hp_sformer_unpatchify": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
     "hp_sformer_joint_token_backward": (_i, [_fp, _fp, _i, _i, C.c_long, _i, _vp]),
+    "hp_tokens_assemble_forward": (_i, [_fp, _fp, _fp, _fp, _i, _i, C.c_long, _i, C.c_long, _vp]),
+    "hp_tokens_assemble_backward": (_i, [_fp, _fp, _fp, _fp, _i, _i, C.c_long, _i, C.c_long, _vp]),
     "hp_optim_adam_multi_workspace_bytes": (_sz, [_i]),
     "hp_optim_adam_multi": (_i, [_vp, _i, _d, _d, _d, _d, _vp, _sz, _vp]),
     "hp_optim_sgd_multi_workspace_bytes": (_sz, [_i]),

@@ -1,8 +1,9 @@
 """Building blocks shared by the transformer heads (transformer.TimeSformer, tokenpose.TokenPose_L_base): every
 arithmetic step is a kernel of libhiddenpose_hip.so (Linear = the MFMA GEMM, LayerNorm, qkv split + rotary,
 flash-style attention, GEGLU / GELU); PyTorch only owns the buffers.  These are the no-graph (inference) forms; the
-training paths of the heads are in _xformer_autograd.py, which shares attention_forward, embed_tokens, add_position_embedding
-and time_perm / time_unperm with them."""
+training paths of the heads are in _xformer_autograd.py, which shares attention_forward, embed_tokens, assemble_tokens (the
+rotary_emb=False heads' assembly with their learned position table), add_position_embedding and time_perm / time_unperm with
+them."""
 from __future__ import annotations
 
 import torch
@@ -156,6 +157,31 @@ def embed_tokens(video, patch, weight, bias, lead):
     x = torch.empty(b, nl + emb.shape[0] // b, dim, dtype=torch.float32, device=video.device)
     x[:, :nl] = lead
     x[:, nl:] = emb.view(b, -1, dim)
+    return tokens, x
+
+
+def check_table_rows(head, table, nl, f, n):
+    """The learned position table (rows, dim) of a rotary_emb=False head covers tokens 0 .. rows - 1; a clip of f frames of n
+    patches behind nl leading tokens needs nl + f n of them.  A longer clip is an IndexError, as in the reference (whose
+    nn.Embedding lookup raises it), before anything is launched."""
+    ntok, rows = nl + f * n, table.shape[0]
+    if ntok > rows:
+        raise IndexError(f"{head} (rotary_emb=False): ntok {ntok} = {nl} + {f} frames x {n} patches exceeds the position table's "
+                         f"{rows} rows; the longest clip that fits has {max(0, (rows - nl) // n)} frames")
+
+
+def assemble_tokens(video, patch, weight, bias, lead, pos):
+    """embed_tokens plus the learned position table pos (rows, dim), rows >= the token count, added to every token, the
+    leading ones included: [lead | Linear(tokens)] + pos[:ntok] in one pass (hp_tokens_assemble_forward), where embed_tokens is
+    two slice copies.  -> (tokens, x)."""
+    b = video.shape[0]
+    tokens = patchify(video, patch)
+    emb = linear(tokens, weight, bias)
+    nl, dim = lead.shape[-2], emb.shape[1]
+    ntok = nl + emb.shape[0] // b
+    x = torch.empty(b, ntok, dim, dtype=torch.float32, device=video.device)
+    _lib.check(_lib.lib().hp_tokens_assemble_forward(lead.data_ptr(), emb.data_ptr(), pos.data_ptr(), x.data_ptr(), b, nl, ntok, dim,
+                                                     pos.shape[0], _st(video)), "hp_tokens_assemble_forward")
     return tokens, x
 
 

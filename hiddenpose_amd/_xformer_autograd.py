@@ -5,7 +5,8 @@ backward").  PyTorch only allocates, zero-fills and copies.
 
 The op-level helpers (layernorm_backward, linear_backward, geglu_backward, gelu_backward) are written for any row-major
 token matrix; all three Functions are built from the same sublayer helpers (pre-norm attention, GEGLU / GELU feed-forward)
-and the token assembly of _xformer.embed_tokens with its adjoint.
+and the token assembly of _xformer.embed_tokens with its adjoint (rotary_emb=False: _xformer.assemble_tokens and
+assemble_tokens_backward, one HIP pass each).
 
 Dropout.  Every nn.Dropout of the reference modules is a *site*: its position in the reference's forward
 order.  A Function takes `drop`, None or (seed, step, p, p) with the module's two probabilities; a sublayer helper takes
@@ -388,11 +389,27 @@ def _joint_sum(dx, rows):
     return out
 
 
-def embed_tokens_backward(dx, tokens, weight, lead_rows, video_shape, patch, need_input):
+def assemble_tokens_backward(dx, lead_rows, pos_shape, need_lead, need_pos):
+    """Adjoint of _xformer.assemble_tokens in one pass over dx (b, ntok, dim) (hp_tokens_assemble_backward): -> (dlead (lead_rows,
+    dim), the batch sum of the leading rows, or None unless need_lead; dpos of pos_shape, the batch sum of every row with
+    exact zeros in the table's rows past ntok, or None unless need_pos; demb (b, ntok - lead_rows, dim), the patch rows'
+    contiguous copy for embed_tokens_backward)."""
+    b, ntok, dim = dx.shape
+    dev = dx.device
+    dlead = torch.empty(lead_rows, dim, dtype=torch.float32, device=dev) if need_lead else None
+    dpos = torch.empty(pos_shape, dtype=torch.float32, device=dev) if need_pos else None
+    demb = torch.empty(b, ntok - lead_rows, dim, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().hp_tokens_assemble_backward(dx.data_ptr(), _lib.ptr(dlead), _lib.ptr(dpos), demb.data_ptr(), b, lead_rows, ntok,
+                                                      dim, pos_shape[0], _st(dx)), "hp_tokens_assemble_backward")
+    return dlead, dpos, demb
+
+
+def embed_tokens_backward(dx, tokens, weight, lead_rows, video_shape, patch, need_input, demb=None):
     """Adjoint of _xformer.embed_tokens below the lead_rows leading rows of dx (b, ntok, dim): -> (dvideo (b, f, c, H, W), or
-    None unless need_input; dW; db) through the embedding's Linear and unpatchify."""
+    None unless need_input; dW; db) through the embedding's Linear and unpatchify.  demb: those rows' contiguous copy where
+    assemble_tokens_backward has made it already."""
     b, f, c, H, W = video_shape
-    demb = dx[:, lead_rows:].contiguous().view(tokens.shape[0], -1)
+    demb = (dx[:, lead_rows:].contiguous() if demb is None else demb).view(tokens.shape[0], -1)
     dtok, dw, db = linear_backward(tokens, demb, weight, need_dx=need_input)
     dvideo = None
     if need_input:
@@ -412,10 +429,17 @@ def _layer_params(layer):
 PER_LAYER = 11
 
 
+def _table_param(m):
+    """[the learned position table] of a rotary_emb=False head, [] of a rotary one."""
+    table = m.position_table()
+    return [] if table is None else [table]
+
+
 def trainable_params(m):
     """The parameters the forward reads, in the order SformerFunction takes them (the time-attention weights, allocated
-    but never run, are not among them: their .grad stays None)."""
-    ps = [m.to_patch_embedding.weight, m.to_patch_embedding.bias, m.joints_token]
+    but never run, are not among them: their .grad stays None).  With rotary_emb=False the position table follows
+    joints_token."""
+    ps = [m.to_patch_embedding.weight, m.to_patch_embedding.bias, m.joints_token] + _table_param(m)
     for layer in m.layers:
         ps += _layer_params(layer)
     ps += [m.to_out[0].weight, m.to_out[0].bias, m.to_out[1].weight, m.to_out[1].bias]
@@ -426,7 +450,9 @@ class SformerFunction(torch.autograd.Function):
     """video (b, f, c, H, W), module, three precisions, drop, *trainable_params(m) -> (b, num_joints, 4, out_dim / 4).
     Per layer: space attention (the axial tables, groups = f frames of hp*wp patches behind the num_joints joint tokens) and
     GEGLU feed-forward.  drop: None or (seed, step, attn_dropout, ff_dropout); sites per layer: 2 i the spatial attention's
-    to_out, 2 i + 1 the feed-forward's hidden activation (the time attention is never run and has no site)."""
+    to_out, 2 i + 1 the feed-forward's hidden activation (the time attention is never run and has no site).
+    With rotary_emb=False params[3] is the position table: the token matrix is assembled with it (X.assemble_tokens; not a
+    dropout site) and every attention runs without rotary tables."""
 
     @staticmethod
     def forward(ctx, video, m, prec, aprec, bprec, drop, *params):
@@ -435,16 +461,21 @@ class SformerFunction(torch.autograd.Function):
         ps, nj, heads, dh = m.patch_size, m.num_joints, m.heads, m.dim_head
         hp, wp = H // ps, W // ps
         n = hp * wp
-        tokens, x = X.embed_tokens(video, ps, *params[:3])
+        first = 3 if m.use_rotary_emb else 4     # index of the first layer's parameters
+        if m.use_rotary_emb:
+            tokens, x = X.embed_tokens(video, ps, *params[:3])
+            sin_t, cos_t = m.image_rot_emb.tables(hp, wp, video.device)
+        else:
+            tokens, x = X.assemble_tokens(video, ps, *params[:4])
+            sin_t = cos_t = None
         ntok, dim = x.shape[1:]
-        sin_t, cos_t = m.image_rot_emb.tables(hp, wp, video.device)
         d_attn, d_ff = _split(drop)
         # a 16-bit backward recomputes P from the 16-bit forward's own lse; a 16-bit forward with the fp32 backward (which
         # backward() refuses) keeps none
         need_lse = aprec == 0 or bprec != 0
         saved, consts = [], []
         for i, (_time_attn, spatial, ff) in enumerate(m.layers):
-            lp = params[3 + PER_LAYER * i: 3 + PER_LAYER * (i + 1)]
+            lp = params[first + PER_LAYER * i: first + PER_LAYER * (i + 1)]
             scale, e_a, e_f = spatial.fn.scale, spatial.norm.eps, ff.norm.eps
             x, s_a = prenorm_attention_forward(x, lp[0:5], e_a, scale, heads, dh, nj, n, f, sin_t, cos_t, prec, aprec=aprec,
                                                drop=d_attn, site=2 * i, need_lse=need_lse)
@@ -454,6 +485,7 @@ class SformerFunction(torch.autograd.Function):
         jt = layernorm(x, params[-4], params[-3], m.to_out[0].eps, b * nj, dim, nj, ntok)
         out = linear(jt, params[-2], params[-1])
         ctx.geom = (tuple(video.shape), ps, nj, heads, dh, n, prec, aprec, bprec, m.to_out[0].eps)
+        ctx.first = first
         ctx.consts = consts
         ctx.drops = (d_attn, d_ff)
         ctx.nsaved = len(saved)
@@ -477,16 +509,22 @@ class SformerFunction(torch.autograd.Function):
         del djt
         d_attn, d_ff = ctx.drops
         per = 9 + 3
+        first = ctx.first
         for i in reversed(range(len(ctx.consts))):
             sv = saved[per * i: per * (i + 1)]
-            base = 3 + PER_LAYER * i
+            base = first + PER_LAYER * i
             lp = params[base: base + PER_LAYER]
             scale, e_a, e_f = ctx.consts[i]
             grads[base + 5: base + 11] = geglu_ff_backward(dx, sv[9:12], lp[5:11], e_f, prec, drop=d_ff, site=2 * i + 1)
             grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_a, scale, heads, dh, nj, n, f, sin_t, cos_t, prec,
                                                                bprec=bprec, drop=d_attn, site=2 * i)
-        grads[2] = _joint_sum(dx, nj)      # joints_token (1, nj, dim), shared by the batch
-        dvideo, grads[0], grads[1] = embed_tokens_backward(dx, tokens, params[0], nj, video_shape, ps, ctx.needs_input_grad[0])
+        demb = None
+        if first == 4:     # joints_token and the position table, both shared by the batch, and the patch rows in one pass
+            dlead, grads[3], demb = assemble_tokens_backward(dx, nj, params[3].shape, ctx.needs_input_grad[6 + 2], ctx.needs_input_grad[6 + 3])
+            grads[2] = None if dlead is None else dlead.view(1, nj, dim)
+        else:
+            grads[2] = _joint_sum(dx, nj)      # joints_token (1, nj, dim), shared by the batch
+        dvideo, grads[0], grads[1] = embed_tokens_backward(dx, tokens, params[0], nj, video_shape, ps, ctx.needs_input_grad[0], demb)
         return (dvideo, None, None, None, None, None, *grads)
 
 
@@ -498,8 +536,9 @@ TS_PER_LAYER = 16
 
 
 def timesformer_params(m):
-    """The parameters TimeSformerFunction takes, in its order (every parameter of the module)."""
-    ps = [m.to_patch_embedding.weight, m.to_patch_embedding.bias, m.cls_token]
+    """The parameters TimeSformerFunction takes, in its order (every parameter of the module; with rotary_emb=False the
+    position table follows cls_token)."""
+    ps = [m.to_patch_embedding.weight, m.to_patch_embedding.bias, m.cls_token] + _table_param(m)
     for time_attn, spatial, ff in m.layers:
         for sub in (time_attn, spatial):
             a = _unwrap(sub.fn, m.shift_tokens)
@@ -516,7 +555,9 @@ class TimeSformerFunction(torch.autograd.Function):
     attention's, 3 i + 2 the feed-forward's hidden activation), *timesformer_params(m) -> (b, 72).
     Per layer: time attention (the rotary frame tables, on the transposed token grid: groups = hp*wp patch positions of f
     tokens; every query applies the mask), space attention (the axial tables, groups = f frames of hp*wp patches; only the
-    class query applies it), GEGLU feed-forward; token shift before each when m.shift_tokens."""
+    class query applies it), GEGLU feed-forward; token shift before each when m.shift_tokens.
+    With rotary_emb=False params[3] is the position table: the token matrix is assembled with it (X.assemble_tokens; not a
+    dropout site) and both attentions run without rotary tables."""
 
     @staticmethod
     def forward(ctx, video, m, prec, aprec, bprec, mask_nat, mask_time, drop, *params):
@@ -529,16 +570,21 @@ class TimeSformerFunction(torch.autograd.Function):
         hp, wp = H // ps, W // ps
         n = hp * wp
         dev = video.device
-        tokens, x = X.embed_tokens(video, ps, *params[:3])
+        first = 3 if m.use_rotary_emb else 4     # index of the first layer's parameters
+        if m.use_rotary_emb:
+            tokens, x = X.embed_tokens(video, ps, *params[:3])
+            sin_s, cos_s = m.image_rot_emb.tables(hp, wp, dev)
+            sin_t, cos_t = m._frame_tables(f, dev)
+        else:
+            tokens, x = X.assemble_tokens(video, ps, *params[:4])
+            sin_s = cos_s = sin_t = cos_t = None
         ntok, dim = x.shape[1:]
-        sin_s, cos_s = m.image_rot_emb.tables(hp, wp, dev)
-        sin_t, cos_t = m._frame_tables(f, dev)
         pre = (lambda t: _token_shift(t, f)) if m.shift_tokens else None
         perm, unperm = (lambda t: X.time_perm(t, f, n)), (lambda t: X.time_unperm(t, f, n))
         saved, consts = [], []
         d_attn, d_ff = _split(drop)
         for i, (time_attn, spatial, ff) in enumerate(m.layers):
-            lp = params[3 + TS_PER_LAYER * i: 3 + TS_PER_LAYER * (i + 1)]
+            lp = params[first + TS_PER_LAYER * i: first + TS_PER_LAYER * (i + 1)]
             sc_t, sc_s = _unwrap(time_attn.fn, m.shift_tokens).scale, _unwrap(spatial.fn, m.shift_tokens).scale
             eps = (time_attn.norm.eps, spatial.norm.eps, ff.norm.eps)
             x, s_t = prenorm_attention_forward(x, lp[0:5], eps[0], sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec, pre, perm, unperm,
@@ -552,6 +598,7 @@ class TimeSformerFunction(torch.autograd.Function):
         out = linear(cls, params[-2], params[-1])
         ctx.geom = (tuple(video.shape), ps, heads, dh, n, prec, m.shift_tokens, m.to_out[0].eps)
         ctx.aprecs = (aprec, bprec)
+        ctx.first = first
         ctx.consts = consts
         ctx.drops = (d_attn, d_ff)
         ctx.nsaved = len(saved)
@@ -584,9 +631,10 @@ class TimeSformerFunction(torch.autograd.Function):
         mask_nat, mask_time = ctx.masks
         d_attn, d_ff = ctx.drops
         per = 9 + 9 + 3
+        first = ctx.first
         for i in reversed(range(len(ctx.consts))):
             sv = saved[per * i: per * (i + 1)]
-            base = 3 + TS_PER_LAYER * i
+            base = first + TS_PER_LAYER * i
             lp = params[base: base + TS_PER_LAYER]
             sc_t, sc_s, e_t, e_s, e_f = ctx.consts[i]
             grads[base + 10: base + 16] = geglu_ff_backward(dx, sv[18:21], lp[10:16], e_f, prec, pre_adj, drop=d_ff, site=3 * i + 2)
@@ -596,8 +644,12 @@ class TimeSformerFunction(torch.autograd.Function):
             grads[base: base + 5] = prenorm_attention_backward(dx, sv[0:9], lp[0:5], e_t, sc_t, heads, dh, 1, f, n, sin_t, cos_t, prec,
                                                                pre_adj, perm, unperm, grouped=grouped, key_mask=mask_time,
                                                                mask_patch_queries=True, drop=d_attn, site=3 * i)
-        grads[2] = _joint_sum(dx, 1).view(1, dim)      # cls_token (1, dim), shared by the batch
-        dvideo, grads[0], grads[1] = embed_tokens_backward(dx, tokens, params[0], 1, video_shape, ps, ctx.needs_input_grad[0])
+        demb = None
+        if first == 4:     # cls_token and the position table, both shared by the batch, and the patch rows in one pass
+            grads[2], grads[3], demb = assemble_tokens_backward(dx, 1, params[3].shape, ctx.needs_input_grad[8 + 2], ctx.needs_input_grad[8 + 3])
+        else:
+            grads[2] = _joint_sum(dx, 1).view(1, dim)      # cls_token (1, dim), shared by the batch
+        dvideo, grads[0], grads[1] = embed_tokens_backward(dx, tokens, params[0], 1, video_shape, ps, ctx.needs_input_grad[0], demb)
         return (dvideo, None, None, None, None, None, None, None, *grads)
 
 

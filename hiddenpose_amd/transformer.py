@@ -32,7 +32,17 @@ adds 1 to `dropout_step` (also under torch.no_grad(), as torch's dropout follows
 of the state_dict.  With `dropout_seed` None nothing changes: a training forward with a probability > 0 is refused, the
 no-grad path ignores dropout.  In eval mode nothing is drawn, with or without a seed.  Sites per layer: the time attention's
 to_out (on the un-permuted rows, as in the reference), the spatial attention's to_out (both attn_dropout), the feed-forward's
-hidden activation after the GEGLU (ff_dropout)."""
+hidden activation after the GEGLU (ff_dropout).
+
+`rotary_emb=False` (:182-187, :229-235) is the learned-position variant: the module owns `pos_emb = nn.Embedding(num_frames *
+num_patches + 1, dim)` (default initialisation; the checkpoint key is `pos_emb.weight`) and neither rotary module.  The table's
+first ntok rows are added to the token matrix, class token included, once before the first layer -- in the pass that assembles
+[class | patch embedding] (hp_tokens_assemble_forward; its adjoint hp_tokens_assemble_backward gives the table's, the class
+token's and the patch embedding's gradients from one read of the token gradient) -- and every attention of every
+layer then runs without rotation (rot_dim 0: the class query sees K0 = K), masked and 16-bit entries alike.  A clip shorter
+than num_frames uses the table's prefix and leaves an exactly zero gradient in the rows behind it; a clip with more tokens than
+the table has rows raises IndexError before anything is launched.  mask, shift_tokens, the precisions and dropout compose with
+it unchanged (the table add is not a dropout site).  A frozen table (requires_grad False) gets no gradient and costs none."""
 from __future__ import annotations
 
 from math import log, pi
@@ -82,20 +92,27 @@ class TimeSformer(nn.Module):
                  dim_head=64, attn_dropout=0.0, ff_dropout=0.0, rotary_emb=True, shift_tokens=False):
         super().__init__()
         assert image_size % patch_size == 0, "Image dimensions must be divisible by the patch size."
-        assert rotary_emb, "only the rotary-embedding variant is built"
         _lib.lib()
         self.heads, self.dim_head, self.patch_size, self.num_frames, self.shift_tokens = heads, dim_head, patch_size, num_frames, shift_tokens
         self.attn_dropout, self.ff_dropout = attn_dropout, ff_dropout
         self.dropout_step = 0   # training forwards drawn so far with dropout active (plain attribute, not in the state_dict)
         self.to_patch_embedding = nn.Linear(channels * patch_size ** 2, dim)
         self.cls_token = nn.Parameter(torch.randn(1, dim))
-        self.frame_rot_emb = RotaryEmbedding(dim_head)
-        self.image_rot_emb = AxialRotaryEmbedding(dim_head)
+        self.use_rotary_emb = rotary_emb
+        if rotary_emb:
+            self.frame_rot_emb = RotaryEmbedding(dim_head)
+            self.image_rot_emb = AxialRotaryEmbedding(dim_head)
+        else:   # :186-187: one learned row per token of a full clip, the class token's first
+            self.pos_emb = nn.Embedding(num_frames * (image_size // patch_size) ** 2 + 1, dim)
         wrap = (lambda m: _PreTokenShift(num_frames, m)) if shift_tokens else (lambda m: m)
         self.layers = nn.ModuleList([
             nn.ModuleList([_PreNorm(dim, wrap(_Attention(dim, dim_head, heads))), _PreNorm(dim, wrap(_Attention(dim, dim_head, heads))),
                            _PreNorm(dim, wrap(_FeedForward(dim)))]) for _ in range(depth)])
         self.to_out = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, 24 * 3))
+
+    def position_table(self):
+        """The learned position table (num_frames * num_patches + 1, dim) of the rotary_emb=False variant, else None."""
+        return None if self.use_rotary_emb else self.pos_emb.weight
 
     def _frame_tables(self, f, device):
         freqs = torch.arange(f, device=device, dtype=torch.float32)[:, None] * self.frame_rot_emb.inv_freqs.to(device)[None, :]
@@ -126,6 +143,9 @@ class TimeSformer(nn.Module):
         with a dropout probability > 0 needs dropout_seed (module docstring).  Otherwise the no-graph path runs, launch for
         launch as an inference-only module would.  With dropout active the forward always goes through
         TimeSformerFunction, under no_grad too, and adds 1 to dropout_step."""
+        if not self.use_rotary_emb:
+            ps = self.patch_size
+            X.check_table_rows("TimeSformer", self.pos_emb.weight, 1, video.shape[1], (video.shape[-2] // ps) * (video.shape[-1] // ps))
         if not video.is_cuda:
             raise _lib.HiddenPoseHipError("TimeSformer.forward needs a tensor on a HIP device; there is no CPU path")
         masks = (None, None)
@@ -156,10 +176,15 @@ class TimeSformer(nn.Module):
         aprec, _ = X.attention_precisions(self, dh, training=False)
         dev = video.device
         with torch.cuda.device(dev):
-            _, x = X.embed_tokens(video, ps, self.to_patch_embedding.weight, self.to_patch_embedding.bias, self.cls_token)
+            if self.use_rotary_emb:
+                _, x = X.embed_tokens(video, ps, self.to_patch_embedding.weight, self.to_patch_embedding.bias, self.cls_token)
+                sin_s, cos_s = self.image_rot_emb.tables(hp, wp, dev)
+                sin_t, cos_t = self._frame_tables(f, dev)
+            else:   # the learned table goes into the token matrix once; every attention then runs without rotation
+                _, x = X.assemble_tokens(video, ps, self.to_patch_embedding.weight, self.to_patch_embedding.bias, self.cls_token,
+                                         self.pos_emb.weight)
+                sin_s = cos_s = sin_t = cos_t = None
             ntok, dim = x.shape[1:]
-            sin_s, cos_s = self.image_rot_emb.tables(hp, wp, dev)
-            sin_t, cos_t = self._frame_tables(f, dev)
             rows = b * ntok
             for time_attn, spatial_attn, ff in self.layers:
                 unwrap = (lambda m: m.fn) if self.shift_tokens else (lambda m: m)

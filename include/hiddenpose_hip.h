@@ -675,6 +675,28 @@ int hp_sformer_unpatchify(const float* tokens, float* video, int B, int frames, 
                           void* stream);
 /* joints_token gradient: djt (num_joints, dim) = sum over the batch of dx[b, :num_joints] (dx (B, Ntok, dim)) */
 int hp_sformer_joint_token_backward(const float* dx, float* djt, int B, int num_joints, long Ntok, int dim, void* stream);
+/* Token assembly of the heads' entry with a learned position table (rotary_emb=False), one pass each way.
+ *
+ * Forward:  x[b, t, :] = (t < nl ? lead[t, :] : emb[b, t - nl, :]) + (pos ? pos[t, :] : 0)   for b < B, t < Ntok.
+ * lead (nl, dim): the class / joint tokens every sample shares (may be NULL when nl == 0); emb (B, Ntok - nl, dim): the patch
+ * embedding; pos (pos_rows, dim): the table, of which the first Ntok rows are read, or NULL: x is then the plain assembly,
+ * bit for bit the copies it replaces (nothing is added, so -0 stays -0).  One rounding per element with pos.
+ *
+ * Backward: reads dx (B, Ntok, dim) once.  Each of the three outputs may be NULL (all three: HP_OK, no launch).
+ *   dpos (pos_rows, dim): dpos[t, :] = sum_b dx[b, t, :] for t < Ntok, and exactly 0 for Ntok <= t < pos_rows: the whole table
+ *     gradient is written, the caller zero-fills nothing;
+ *   dlead (nl, dim): the first nl rows of the same sum;
+ *   demb (B, Ntok - nl, dim): demb[b, t - nl, :] = dx[b, t, :], the contiguous copy the patch embedding's weight gradient reads.
+ * The sum starts from dx[0] and adds dx[1], dx[2], ... in ascending b in one thread per element: no float atomics, a fixed
+ * order, two calls give equal bits.
+ *
+ * Both: B >= 1, dim >= 1, nl >= 0, Ntok > nl; Ntok > pos_rows with a non-NULL pos / dpos is HP_ERR_BAD_ARG (pos_rows is not
+ * read otherwise); every refusal comes before any device call.  Any 4-byte alignment: 16-byte accesses when dim % 4 == 0 and
+ * every given base is 16-byte aligned, 4-byte ones otherwise, with the same bits.  No two buffers may overlap. */
+int hp_tokens_assemble_forward(const float* lead, const float* emb, const float* pos, float* x, int B, int nl, long Ntok, int dim,
+                               long pos_rows, void* stream);
+int hp_tokens_assemble_backward(const float* dx, float* dlead, float* dpos, float* demb, int B, int nl, long Ntok, int dim,
+                                long pos_rows, void* stream);
 
 /* ------------------------------------------------------------------------
  * Optimizer stage (train.py:131 `optim.Adam(params, lr)`, models/optimizer.py's SGD branch): torch's update rules over a

@@ -6,8 +6,12 @@ time in fp32 (from the step) and with fp16 patch attention (a no-graph forward o
 
     python tools/time_sformer_train.py [--batch 8] [--steps 5] [--warmup 2] [--heads 8] [--dim-head 32]
                                        [--attention fp32|bf16|fp16] [--attention-backward fp32|bf16|fp16] [--linear fp32|bf16]
-                                       [--dropout P] [--ab-rounds 5]
+                                       [--dropout P] [--ab-rounds 5] [--no-rotary] [--ab-calls 20]
 
+--no-rotary builds the module with rotary_emb=False (the learned position table).  Its table has 16 * 1024 + 1
+rows of which the 24 joint tokens take 24, so the longest clip that fits has 15 frames: every figure is then taken on 15
+frames.  "token_assembly_ab" adds the token assembly alone at that geometry, forward + backward, the two HIP entries against
+the copy-and-add composition they replace (tools/time_xformer_train.py token_assembly_ab; median of --ab-calls calls).
 --dropout P sets attn_dropout = ff_dropout = P and a dropout_seed (seeded Philox dropout): every figure is then
 taken with dropout active, and "dropout_ab" adds the step with dropout 0 against dropout P in alternating rounds.
 --attention / --attention-backward are NlosPoseSformer.attention_precision / attention_backward_precision (a 16-bit forward
@@ -78,11 +82,14 @@ def main():
     ap.add_argument("--attention", choices=("fp32", "bf16", "fp16"), default="fp32")
     ap.add_argument("--attention-backward", choices=("fp32", "bf16", "fp16"), default="fp32")
     ap.add_argument("--linear", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--no-rotary", action="store_true", help="rotary_emb=False on the longest clip that fits (15 frames)")
+    ap.add_argument("--ab-calls", type=int, default=20, help="timed calls per leg of the token assembly's A/B")
     a = ap.parse_args()
     if a.attention != "fp32" and a.attention_backward == "fp32":
         ap.error("a 16-bit --attention trains only with a 16-bit --attention-backward")
     kw = dict(dim=256, num_frames=16, num_joints=24, image_size=128, patch_size=4, channels=1, depth=8, heads=a.heads,
-              dim_head=a.dim_head, out_dim=512)
+              dim_head=a.dim_head, out_dim=512, rotary_emb=not a.no_rotary)
+    frames = 15 if a.no_rotary else 16
     m = NlosPoseSformer(**kw)
     hpt.fill_module(m, "sformer.")
     m = m.cuda()
@@ -94,7 +101,7 @@ def main():
 
     set_dropout(a.dropout)
     B = a.batch
-    video = torch.rand(B, 16, 1, 128, 128, generator=torch.Generator().manual_seed(5)).cuda()
+    video = torch.rand(B, frames, 1, 128, 128, generator=torch.Generator().manual_seed(5)).cuda()
     R = torch.randn(B, 24, 4, 128, generator=torch.Generator().manual_seed(6)).cuda()
 
     def fwd_nograd():
@@ -144,14 +151,19 @@ def main():
     patch_fp16_ms = prof16.get("sformer_attention_patch", (0, 0.0))[1]
     _lib.profile_enable(False)
     m.attention_precision = a.attention
-    f, n, nj, heads, dh, depth = 16, 32 * 32, 24, a.heads, a.dim_head, 8
+    f, n, nj, heads, dh, depth = frames, 32 * 32, 24, a.heads, a.dim_head, 8
     ntok = nj + f * n
     flops = depth * (5 * 2 * B * heads * f * n * (nj + n) * dh + 5 * 2 * B * heads * nj * ntok * dh)
     attn_ms = sum(ms for k, (_, ms) in prof.items() if k.startswith("sformer_attn_bwd"))
     rate = flops / (attn_ms * 1e-3) if attn_ms else 0.0
     exps = depth * 2 * (B * heads * f * n * (nj + n) + B * heads * nj * ntok)
+    assembly = None
+    if a.no_rotary:
+        from time_xformer_train import token_assembly_ab
+
+        assembly = token_assembly_ab(B, nj, ntok, kw["dim"], m.pose_emb.weight.shape[0], a.ab_calls)
     print(json.dumps({
-        "config": "config5", "batch": B, "precision": a.linear, "attention": a.attention, "attention_backward": a.attention_backward,
+        "config": "config5", "batch": B, "rotary_emb": not a.no_rotary, "frames": frames, "token_assembly_ab": assembly, "precision": a.linear, "attention": a.attention, "attention_backward": a.attention_backward,
         "heads": a.heads, "dim_head": a.dim_head, "dropout": a.dropout, "dropout_ab": ab,
         "forward_nograd_ms": round(t_nograd, 2), "forward_graph_ms": round(t_graph, 2),
         "backward_ms": round(t_step - t_graph, 2), "step_ms": round(t_step, 2), "step_over_nograd_forward": round(t_step / t_nograd, 2),

@@ -8,8 +8,13 @@ inputs, same process, median of the timed calls); the device's maxGridSize; and 
     python tools/time_xformer_train.py [--steps 5] [--warmup 2] [--ab-calls 20] [--heads 8] [--dim-head 32]
                                        [--valid-frames K] [--timesformer-only]
                                        [--attention fp32|bf16|fp16] [--attention-backward fp32|bf16|fp16] [--linear fp32|bf16]
-                                       [--dropout P] [--ab-rounds 5]
+                                       [--dropout P] [--ab-rounds 5] [--no-rotary]
 
+--no-rotary builds TimeSformer with rotary_emb=False (the learned position table; TokenPose-L has no such
+switch and runs as always) and adds "token_assembly_ab": the token assembly alone at the step's geometry, forward + backward,
+hp_tokens_assemble_forward / _backward against the copy-and-add composition they replace (two slice copies and an add of a
+batch-sized copy of the table; two batch sums, a zero-filled table tail and a slice copy), median of --ab-calls timed calls
+each, alternating.
 --dropout P sets every dropout probability of both heads to P and a dropout_seed (seeded Philox dropout): the
 heads' figures are then taken with dropout active, and each head's "dropout_ab" adds the step with dropout 0 against dropout
 P in alternating rounds.
@@ -131,6 +136,52 @@ def head_timing(m, x, R, steps, warmup, dropout=0.0, ab_rounds=5, **fkw):
     }
 
 
+def token_assembly_ab(B, nl, ntok, dim, rows, calls):
+    """Forward + backward of the token assembly with a position table (rows, dim) at (B, ntok, dim) behind nl leading tokens:
+    the two HIP entries against the stock composition they replace, same inputs, same process, alternating calls."""
+    from hiddenpose_amd import hip_ops as ops
+
+    g = torch.Generator().manual_seed(11)
+    lead, emb, pos, dx = (torch.randn(s, generator=g).cuda() for s in ((1, nl, dim), (B, ntok - nl, dim), (rows, dim), (B, ntok, dim)))
+    L, st = _lib.lib(), _lib.current_stream_handle(dx.device)
+
+    def kernel():
+        x = torch.empty(B, ntok, dim, device=dx.device)
+        _lib.check(L.hp_tokens_assemble_forward(lead.data_ptr(), emb.data_ptr(), pos.data_ptr(), x.data_ptr(), B, nl, ntok, dim, rows, st),
+                   "hp_tokens_assemble_forward")
+        return (x, *xa.assemble_tokens_backward(dx, nl, pos.shape, True, True))
+
+    def composition():
+        x = torch.empty(B, ntok, dim, device=dx.device)
+        x[:, :nl] = lead
+        x[:, nl:] = emb
+        x = ops.add(x, pos[None, :ntok].expand(B, -1, -1).contiguous())
+        dpos = torch.zeros(rows, dim, device=dx.device)
+        dpos[:ntok] = xa._joint_sum(dx, ntok)[0]
+        return x, xa._joint_sum(dx, nl)[0], dpos, dx[:, nl:].contiguous()
+
+    outs, ts = {}, {"kernel": [], "composition": []}
+    for name, fn in (("kernel", kernel), ("composition", composition)):
+        for _ in range(3):
+            outs[name] = fn()
+    for _ in range(calls):
+        for name, fn in (("kernel", kernel), ("composition", composition)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts[name].append(e0.elapsed_time(e1))
+    res = {name + "_ms": round(statistics.median(v), 4) for name, v in ts.items()}
+    res["kernel_over_composition"] = round(res["kernel_ms"] / res["composition_ms"], 3)
+    # what one forward + backward must move at the least: emb, x, dx, demb once each, the table three times (pos, dpos, lead rows)
+    least = 4 * (2 * B * ntok * dim + 2 * B * (ntok - nl) * dim + 2 * rows * dim + 2 * nl * dim)
+    res["kernel_gb_per_s_on_least_traffic"] = round(least / (res["kernel_ms"] * 1e-3) / 1e9, 1)
+    res["bit_equal"] = [bool(torch.equal(a, b)) for a, b in zip(outs["kernel"], outs["composition"])]
+    res["geometry"] = {"batch": B, "lead_rows": nl, "ntok": ntok, "dim": dim, "table_rows": rows, "calls": calls}
+    return res
+
+
 def time_attention_ab(m, B, calls):
     """Time attention's backward of layer 0 on saved inputs of a real forward: grouped vs generic entry."""
     f, hp = TS_KW["num_frames"], TS_KW["image_size"] // TS_KW["patch_size"]
@@ -140,7 +191,7 @@ def time_attention_ab(m, B, calls):
     x = torch.randn(B, ntok, dim, generator=g).cuda()
     time_attn = m.layers[0][0]
     p = (time_attn.norm.weight, time_attn.norm.bias, time_attn.fn.to_qkv.weight, time_attn.fn.to_out[0].weight, time_attn.fn.to_out[0].bias)
-    sin_t, cos_t = m._frame_tables(f, x.device)
+    sin_t, cos_t = m._frame_tables(f, x.device) if m.use_rotary_emb else (None, None)
     with torch.no_grad():
         _, sv = xa.prenorm_attention_forward(x, p, time_attn.norm.eps, time_attn.fn.scale, heads, dh, 1, f, n, sin_t, cos_t, 0,
                                              perm=lambda t: xf.time_perm(t, f, n), unperm=lambda t: xf.time_unperm(t, f, n))
@@ -204,10 +255,11 @@ def main():
     ap.add_argument("--linear", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--dropout", type=float, default=0.0, help="every dropout probability of both heads, with a dropout_seed")
     ap.add_argument("--ab-rounds", type=int, default=5, help="alternating rounds of the dropout 0 / P comparison")
+    ap.add_argument("--no-rotary", action="store_true", help="TimeSformer with rotary_emb=False, and the token assembly's A/B")
     a = ap.parse_args()
     if a.attention != "fp32" and a.attention_backward == "fp32":
         ap.error("--attention bf16 / fp16 needs --attention-backward bf16 / fp16 (the 16-bit patch attention has no fp32 backward)")
-    TS_KW.update(heads=a.heads, dim_head=a.dim_head or TS_KW["dim_head"])
+    TS_KW.update(heads=a.heads, dim_head=a.dim_head or TS_KW["dim_head"], rotary_emb=not a.no_rotary)
     if a.dim_head:
         assert TP_KW["dim"] % a.dim_head == 0, "TokenPose-L: dim 192 must be a multiple of --dim-head"
         TP_KW.update(heads=TP_KW["dim"] // a.dim_head)
@@ -216,6 +268,9 @@ def main():
     hpt.fill_module(ts, "timesformer.")
     ts = ts.cuda()
     ts.attention_precision, ts.attention_backward_precision, ts.linear_precision = a.attention, a.attention_backward, a.linear
+    out["rotary_emb"] = not a.no_rotary
+    if a.no_rotary:
+        out["token_assembly_ab"] = token_assembly_ab(4, 1, 1 + 16 * 1024, TS_KW["dim"], ts.pos_emb.weight.shape[0], a.ab_calls)
     out["geometry"] = {"timesformer": [TS_KW["heads"], TS_KW["dim_head"]], "tokenpose_l": [TP_KW["heads"], TP_KW["dim"] // TP_KW["heads"]]}
     if a.timesformer_only:
         out["timesformer_time_attention_backward_ab"] = {"skipped": "--timesformer-only"}
