@@ -188,6 +188,9 @@ SIGNATURES = {
                                    _vp]),
     "hp_simdr_loss_backward": (_i, [_fp, _i, C.c_long, _fp, _i, C.c_long, _fp, _i, C.c_long, _fp, _fp, _i, _i, _d, _fp, _fp, _fp, _fp,
                                     _fp, _vp]),
+    "hp_volume_views_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "hp_volume_views": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "hp_views_orient": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
 }
 
 

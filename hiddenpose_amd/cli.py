@@ -22,6 +22,11 @@ def parse_args(argv=None):
     p.add_argument("--max-steps", type=int, default=None, help="stop every epoch after this many iterations")
     p.add_argument("--epochs", type=int, default=None, help="override TRAIN.END_EPOCH")
     p.add_argument("--realdata", type=str, default="data/lct256_human.mat")
+    # the reference's logging step (utils/train_epoch.py:49-72, test.py:163-167), reduced on the device; off by default
+    p.add_argument("--views-every", type=int, default=None,
+                   help="train.py: every N iterations write the projections, three views and joint plots under ./results")
+    p.add_argument("--views", type=str, default="", metavar="DIR",
+                   help="test.py (test_realdata, test_fk): write the three views of the feature volume and the joints figure to DIR")
     return p.parse_args(argv)
 
 

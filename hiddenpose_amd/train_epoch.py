@@ -3,8 +3,10 @@
 Counterpart of utils/train_epoch.py:32-104 (inner loop), train.py:97-229 (seed 410,
 Adam 1e-3, MultiStepLR([2,4,13], 0.2) stepped BEFORE each epoch, checkpoint dict) and
 test.py:138-238 (eval = model.eval() + soft-argmax decode).  Host I/O of the reference
-loop (np.savetxt every step, matplotlib dumps, per-step loss.item() sync) is not part of
-the hot path and is left to the caller.
+loop (np.savetxt every step, per-step loss.item() sync) is not part of the hot path and is
+left to the caller; its logging step (train_epoch.py:49-72: projections, three views, joint
+plots) is opt-in through `views_every` and reduces the volumes on the device
+(hiddenpose_amd.visualizer).
 """
 from __future__ import annotations
 
@@ -52,10 +54,13 @@ def compute_loss(model, criterion, voxel_criterion, meas, vol, target_joints):
     return loss, joint_loss, voxel_loss, output, feature
 
 
-def train_step(model, criterion, voxel_criterion, optimizer, meas, vol, target_joints, reducer=None):
+def train_step(model, criterion, voxel_criterion, optimizer, meas, vol, target_joints, reducer=None, return_outputs=False):
     """One iteration of train_epoch.py:32-76: forward, loss, zero_grad, backward, step.
-    With a GradBucketReducer the gradient all-reduce overlaps backward."""
-    loss, jl, vl, _, _ = compute_loss(model, criterion, voxel_criterion, meas, vol, target_joints)
+    With a GradBucketReducer the gradient all-reduce overlaps backward.  return_outputs=True appends the step's detached
+    `output` and `feature` to the three losses (the logging step of train_epoch needs them)."""
+    loss, jl, vl, output, feature = compute_loss(model, criterion, voxel_criterion, meas, vol, target_joints)
+    if not return_outputs:
+        output = None   # unless asked for, the heat-maps are not held through backward: their block is the allocator's to reuse
     if reducer is not None:
         reducer.zero_grad()
     else:
@@ -66,7 +71,38 @@ def train_step(model, criterion, voxel_criterion, optimizer, meas, vol, target_j
             reducer.finish()
     with R.stage("optimizer"):
         optimizer.step()
+    if return_outputs:
+        return loss.detach(), jl.detach(), vl.detach(), output.detach(), feature.detach()
     return loss.detach(), jl.detach(), vl.detach()
+
+
+@torch.no_grad()
+def log_views(cfg, output, feature, vol, target_joints, global_iter_num, views_dir="./results"):
+    """The logging step of utils/train_epoch.py:49-72 under `views_dir` (the reference's "./results"): volume_log and
+    threeviews_log of vol, output and feature, joints_log of sample 0's decoded prediction and ground truth -- eight items.
+    The marks of volume_log are sample 0's target joints (the reference's ./1.txt).  Returns what the loggers returned."""
+    from . import visualizer as V
+
+    it = global_iter_num
+    nj = cfg.DATASET.NUM_JOINTS
+    hm = cfg.DATASET.HEATMAP_SIZE
+    gt = target_joints[0].reshape(nj, 3).detach().cpu().numpy()
+    out = {}
+    for name, t in (("volume", vol), ("output", output), ("feature", feature)):
+        out[f"volume_log/{name}"] = V.volume_log(t, f"{views_dir}/volume", f"{name}_{it}", it, joints=gt)
+    preds = softmax_integral_tensor(output, nj, True, hm[0], hm[1], hm[2])
+    out["pred_joints"] = V.joints_log(preds[0].reshape(nj, 3).detach().cpu().numpy(), f"{views_dir}/figure/joints",
+                                      f"pred_joints_{it}", it)
+    out["gt_joints"] = V.joints_log(gt, f"{views_dir}/figure/joints", f"gt_joints_{it}", it)
+    for name, t in (("feature", feature), ("output", output), ("volume", vol)):
+        out[f"threeviews_log/{name}"] = V.threeviews_log(t, f"{views_dir}/figure/threeviews", f"{name}_{it}", it)
+    return out
+
+
+def _is_rank0() -> bool:
+    import torch.distributed as dist
+
+    return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
 
 
 def checkpoint_dict(model, optimizer, lr_scheduler, epoch, global_iter_num=None):
@@ -105,12 +141,14 @@ def predict_joints(model, meas, cfg):
 
 
 def train_epoch(cfg, train_loader, model, criterion, voxel_criterion, optimizer, epoch, output_dir, writer, begin_time,
-                save_model_dir, lr_scheduler, reducer=None, max_steps=None):
+                save_model_dir, lr_scheduler, reducer=None, max_steps=None, views_every=None, views_dir="./results"):
     """One epoch with the call signature of utils/train_epoch.py:20-104 (positional order as train.py:162 passes it).
     Per batch: forward, L2Joint + BCEDice loss, zero_grad, backward, step; a checkpoint dict every 10000 global
-    iterations (:78-90) and the running 100-iteration loss (:92-97).  The reference's per-step `loss.item()` print,
-    `np.savetxt` and matplotlib dumps are not reproduced: the loss is accumulated on the device and read back once
-    per 100 iterations, so the loop never stalls the GPU.  `writer` may be None.  Returns the mean loss of the epoch."""
+    iterations (:78-90) and the running 100-iteration loss (:92-97).  The reference's per-step `loss.item()` print
+    and `np.savetxt` are not reproduced: the loss is accumulated on the device and read back once per 100 iterations, so the loop never stalls the GPU.  `writer` may be None.  Returns the mean loss of the epoch.
+    views_every=N: every N global iterations the reference's logging step (:49-72, there every 100) runs from that step's own
+    output, feature, vol and joints (`log_views`), on rank 0 under torch.distributed; None (default): never, and
+    hiddenpose_amd.visualizer is not imported."""
     import os
     import time
 
@@ -129,7 +167,14 @@ def train_epoch(cfg, train_loader, model, criterion, voxel_criterion, optimizer,
         meas = torch.as_tensor(meas).to(device=device, dtype=torch.float32)
         vol = torch.as_tensor(vol).to(device=device, dtype=torch.float32)
         target_joints = torch.as_tensor(target_joints).to(device=device, dtype=torch.float32)  # (B, 24, 3)
-        loss, _, _ = train_step(model, criterion, voxel_criterion, optimizer, meas, vol, target_joints, reducer)
+        if views_every and global_iter_num % views_every == 0:
+            loss, _, _, output, feature = train_step(model, criterion, voxel_criterion, optimizer, meas, vol, target_joints, reducer,
+                                                     return_outputs=True)
+            if _is_rank0():
+                log_views(cfg, output, feature, vol, target_joints, global_iter_num, views_dir)
+            del output, feature
+        else:
+            loss, _, _ = train_step(model, criterion, voxel_criterion, optimizer, meas, vol, target_joints, reducer)
         window += loss
         epoch_sum += loss
         steps += 1

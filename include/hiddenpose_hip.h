@@ -803,6 +803,35 @@ int hp_simdr_loss_backward(const float* pred_x, int nx, long stride_x, const flo
                            void* stream);
 
 /* ------------------------------------------------------------------------
+ * Three-view projections of a volume: what utils/visualizer.py reduces on the host after copying whole
+ * volumes there (threeviews_log, :155-185; volume_log, :33-57).  x holds P contiguous fp32 planes (T, H, W).  One read of x
+ * gives, per plane,
+ *   front (P, H, W): over t        top (P, T, W): over h        left (P, T, H): over w
+ * HP_VIEWS_MAX_CLAMPED: maxima of v = max(x, 0).  HP_VIEWS_SUM: plain sums of x, no clamp.  Both: vmax[3 p + {0, 1, 2}] is
+ * the maximum of the finished front / top / left view of plane p.  x is never written.  Reductions across workgroups go
+ * through partial slabs in the workspace and an ordered combine: no atomics, fixed summation order, two calls give equal
+ * bits.  Outputs and workspace need no initialisation.
+ * NaN follows NumPy (`v[v < 0] = 0` leaves a NaN, np.max / np.sum propagate it): a NaN anywhere in a reduced line makes
+ * that pixel NaN and the vmax of that view NaN (max mode: the positive quiet pattern 0x7fc00000 whatever the input's sign
+ * and payload).  +inf propagates as a value; -0.0 and +0.0 count as equal (max mode returns +0.0).
+ * hp_views_orient writes what the reference hands to imshow:
+ *   out_front (P, H, W) = front / vmax_front
+ *   out_top   (P, T, W) = rot90(top / vmax_top, 2):    out[i, j] = n[T-1-i, W-1-j]
+ *   out_left  (P, H, T) = rot90(left / vmax_left, 3):  out[i, j] = n[T-1-j, i]
+ * with the correctly rounded division of NumPy.  One deliberate difference: a view whose maximum is 0 comes out as zeros
+ * (the reference divides 0 by 0 into NaNs with a warning).  A NaN maximum gives a NaN view.
+ * Arguments are checked before any device call.  HP_ERR_BAD_ARG: a null pointer, a non-positive extent, an unknown mode, a
+ * plane of 2^31 voxels or more (offsets inside a plane are 32-bit, across planes 64-bit).  HP_ERR_WORKSPACE: a workspace
+ * smaller than the query, which returns 0 for arguments the call would refuse.
+ * ---------------------------------------------------------------------- */
+enum { HP_VIEWS_MAX_CLAMPED = 0, HP_VIEWS_SUM = 1 };
+size_t hp_volume_views_workspace_bytes(int P, int T, int H, int W, int mode);
+int hp_volume_views(const float* x, float* front, float* top, float* left, float* vmax, int P, int T, int H, int W, int mode,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int hp_views_orient(const float* front, const float* top, const float* left, const float* vmax, float* out_front,
+                    float* out_top, float* out_left, int P, int T, int H, int W, void* stream);
+
+/* ------------------------------------------------------------------------
  * Measurement ingest (utils/nlos_pose_dataloader.py:71-144, utils/loadrealdata.py:6-15): the per-sample
  * CPU work of the reference's Dataset.__getitem__, moved to the device.
  * ---------------------------------------------------------------------- */

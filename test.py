@@ -7,7 +7,9 @@
 eval-mode forward + soft-argmax decode.  test_pose_v2 walks the test split in batches of TEST.BATCH_SIZE, writes
 `./test_results/joints/preds_<id>.txt` / `gt_<id>.txt` (24 x 3, voxel units of the 64^3 heat-map; the reference
 renders them to figures) and prints the MPJPE; test_realdata runs a measured `.mat` volume duplicated to batch 2
-as test.py:183-201 does; test_fk runs every f-k capture `.mat` under --data (test.py:141-170)."""
+as test.py:183-201 does; test_fk runs every f-k capture `.mat` under --data (test.py:141-170).  `--views DIR` (both
+of these) also writes the max-projected front / top / left views of the refined feature volume of every capture to DIR
+and its joints figure to DIR/joints, as test.py:163-167,198-202 does."""
 from __future__ import annotations
 
 import os
@@ -27,6 +29,15 @@ def _decode(model, cfg, meas):
     output, feature = model(meas)
     hm = cfg.DATASET.HEATMAP_SIZE
     return softmax_integral_tensor(output, cfg.DATASET.NUM_JOINTS, True, hm[0], hm[1], hm[2]), feature
+
+
+def _log_views(views_dir, feature, joints, name, idx):
+    """test.py:163-167,198-202 with the reference's file stems: `<DIR>/name_<name>_{front,top,left}_view_<idx>.jpg` from
+    threeviews_log of the feature volume, `<DIR>/joints/<idx>_pred_real_joints_<name>113.png` (and txt/) from joints_log."""
+    from hiddenpose_amd.visualizer import joints_log, threeviews_log
+
+    joints_log(joints, os.path.join(views_dir, "joints"), f"{idx}_pred_real_joints_{name}", 113)
+    return threeviews_log(feature, views_dir, f"name_{name}", idx)
 
 
 def main(argv=None):
@@ -55,10 +66,12 @@ def main(argv=None):
 
             meas = load_realdata(args.realdata, device=dev)                      # (t, w, h)
             meas = meas[None, None].repeat(2, 1, 1, 1, 1).contiguous().float()    # test.py:190
-            preds, _ = _decode(model, cfg, meas)
+            preds, feature = _decode(model, cfg, meas)
             name = os.path.splitext(os.path.basename(args.realdata))[0]
             np.savetxt(os.path.join(out_dir, f"pred_real_joints_{name}.txt"), preds[0].reshape(nj, 3).cpu().numpy())
             result["preds"] = preds[0].reshape(nj, 3).cpu().numpy()
+            if args.views:
+                result["views"] = _log_views(args.views, feature, result["preds"], name, 0)
         elif kind == "test_pose_v2":
             from hiddenpose_amd.nlos_pose_dataloader import NlosPoseDataset
             from train import _collate
@@ -94,10 +107,12 @@ def main(argv=None):
                     x = (x[:, :, ::2] + x[:, :, 1::2]) / 2
                 x = x[:, :, 64:64 + 128].permute(2, 0, 1).contiguous()            # 'h w t -> t h w'
                 meas = x[None, None].repeat(2, 1, 1, 1, 1).contiguous()
-                preds, _ = _decode(model, cfg, meas)
+                preds, feature = _decode(model, cfg, meas)
                 name = os.path.splitext(fname)[0]
                 np.savetxt(os.path.join(out_dir, f"pred_fk_joints_{name}.txt"), preds[0].reshape(nj, 3).cpu().numpy())
                 result["preds"][name] = preds[0].reshape(nj, 3).cpu().numpy()
+                if args.views:
+                    result.setdefault("views", {})[name] = _log_views(args.views, feature, result["preds"][name], name, len(result["preds"]) - 1)
         else:
             raise SystemExit(f"TEST.TYPE {kind!r}: use --test test_pose_v2, test_realdata or test_fk")
     print("finished")

@@ -7,8 +7,10 @@
 
 seed 410; NlosPose at 128 x 128 x 128; NlosPoseDataset with the per-sample ingest on the GPU; Adam(lr 1e-3);
 MultiStepLR([2, 4, 13], 0.2) stepped BEFORE each epoch (train.py:193); L2Joint + BCEDice; a checkpoint dict per
-epoch ({model_state_dict, optimizer_state_dict, lr_scheduler, epoch}).  Under torch.distributed each rank takes
-its own shard of the dataset and gradients are averaged with bucketed RCCL all-reduce overlapped with backward."""
+epoch ({model_state_dict, optimizer_state_dict, lr_scheduler, epoch}).  `--views-every N` writes the reference's
+logging step (projections, three views, joint plots; utils/train_epoch.py:49-72) under ./results every N iterations.
+Under torch.distributed each rank takes its own shard of the dataset and gradients are averaged with bucketed RCCL
+all-reduce overlapped with backward."""
 from __future__ import annotations
 
 import os
@@ -99,7 +101,8 @@ def main(argv=None):
             loader.set_epoch(epoch)
         lr_scheduler.step()  # the reference steps the schedule before the epoch's first optimizer step
         mean_loss = train_epoch(cfg, loader, model, criterion, voxel_criterion, optimizer, epoch, cfg.RESULT.FINAL_OUTPUT_DIR,
-                                writer, begin_time, save_model_dir, lr_scheduler, reducer=reducer, max_steps=args.max_steps)
+                                writer, begin_time, save_model_dir, lr_scheduler, reducer=reducer, max_steps=args.max_steps,
+                                views_every=args.views_every)
         if rank == 0:
             dt = time.time() - t0
             steps = len(loader) if args.max_steps is None else min(len(loader), args.max_steps)
