@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -18,6 +19,20 @@ _lib = None
 
 class HiddenPoseHipError(RuntimeError):
     pass
+
+
+def env_int(name: str, default: int) -> int:
+    """Integer environment switch, read the way C `atoi` reads it (the library latches some of the same switches with atoi):
+    leading digits count, an empty or non-numeric value is 0 and never an error; unset gives `default`."""
+    v = os.environ.get(name)
+    if v is None:
+        return default
+    m = re.match(r"\s*[+-]?\d+", v)
+    return int(m.group()) if m else 0
+
+
+def env_flag(name: str, default: bool) -> bool:
+    return env_int(name, int(default)) != 0
 
 
 # name -> (restype, argtypes); every symbol declared in include/hiddenpose_hip.h

@@ -10,6 +10,7 @@ HIP device.  With HP_OPTIMIZER_IMPL=hip the optimizer is hiddenpose_amd.optimize
 from __future__ import annotations
 
 import os
+import weakref
 
 import torch
 import torch.nn.functional as F
@@ -34,6 +35,7 @@ def _need_cuda(x: torch.Tensor, what: str) -> None:
 import ctypes as _C
 
 from . import _lib
+from . import _side_stream as _side
 
 
 def _stream(t):
@@ -59,8 +61,9 @@ def set_dconv_precision(name: str) -> str:
 # randomly filled network amplifies the operand rounding itself.
 _DCONV_NAMES = ("fp32", "bf16", "bf16emu")
 # A/B switch: HP_DCONV_WGRAD_BF16=0 keeps the weight gradients of the bf16 mode on the exact kernel
-_DCONV_WGRAD_STREAM = bool(int(__import__("os").environ.get("HP_DCONV_WGRAD_STREAM", "1")))   # thin-channel weight gradients on the second stream
+_DCONV_WGRAD_STREAM = _lib.env_flag("HP_DCONV_WGRAD_STREAM", True)   # thin-channel weight gradients on the second stream
 _DCONV_WGRAD_BF16 = os.environ.get("HP_DCONV_WGRAD_BF16", "1") != "0"
+_DCONV_C1_MFMA = _lib.env_flag("HP_DCONV_C1_MFMA", False)   # latched once, as the library latches it (use_mfma_c1, dconv_kernels.hip)
 
 
 def _emu(t, prec, cin, cout):
@@ -71,48 +74,10 @@ _side_dconv_calls = [0]    # thin-channel weight gradients that took the second 
 _side_conv_calls = [0]     # the regressor's
 
 
-def _note_use(w):
-    """Forward half of the shared-weight test of the side-stream weight gradients: a weight used twice in one graph has its two
-    gradients SUMMED by autograd on the main stream, so neither may be written on the side stream.  Called by the Python
-    wrappers right before `Function.apply` -- inside `forward` grad mode is always off and says nothing about the caller's
-    (rounds 3-4 counted there, i.e. never: no model of this package shares a convolution weight, so nothing ever raced).
-    `w._hp_uses`: {forward epoch: uses not yet consumed by a backward}; entries older than 8 epochs are dropped (a graph that was
-    built and never differentiated must not keep a weight off the side stream for the rest of the process)."""
-    if torch.is_grad_enabled() and w is not None and w.requires_grad:
-        ep = _use_epoch[0]
-        d = getattr(w, "_hp_uses", None)
-        if not isinstance(d, dict):
-            d = {}
-        for k in [k for k in d if k < ep - 8]:
-            del d[k]
-        d[ep] = d.get(ep, 0) + 1
-        w._hp_uses = d
-
-
-def _shared_use(ctx, w):
-    """Backward half: True if this weight's gradient must stay on the main stream -- it has more than one outstanding use (in
-    this forward or in another one whose graph may be part of the same backward), or this use was never counted (a caller
-    that bypassed the wrappers: nothing is known).  Releases this use; the flag `_hp_shared` keeps the remaining uses of the
-    pass on the main stream as well."""
-    d = getattr(w, "_hp_uses", None)
-    if not isinstance(d, dict):
-        d = {}
-    total, mine = sum(d.values()), d.get(ctx.use_epoch, 0)
-    shared = total > 1 or mine == 0 or getattr(w, "_hp_shared", False)
-    if total > 1:
-        w._hp_shared = True
-    if mine > 0:
-        if mine == 1:
-            del d[ctx.use_epoch]
-        else:
-            d[ctx.use_epoch] = mine - 1
-        if not d:
-            w._hp_shared = False
-    return shared
-
-
-def _dconv3_grads(x, w, g, replicate, has_bias, need_dx, prec=0, w_param=None, b_param=None):
-    """(dx, dw, db) of y = conv3(x, w) + b given g = dL/dy; planar tensors."""
+def _dconv3_grads(x, w, g, replicate, bias, need_dx, prec, force_main):
+    """(dx, dw, db) of y = conv3(x, w) + b given g = dL/dy; planar tensors.  w, bias: the tensors the forward was called with;
+    force_main: the answer of _side.release."""
+    has_bias = bias is not None
     L = _lib.lib()
     b, cin, d, h, wd = x.shape
     cout = w.shape[0]
@@ -123,7 +88,7 @@ def _dconv3_grads(x, w, g, replicate, has_bias, need_dx, prec=0, w_param=None, b
         gx = torch.empty_like(x)
         # the 1 -> 1 layers (FeatureExtraction) fold the replicate padding inside the stencil kernel: no halo workspace
         # (270 MB at 1024 x 256 x 256) unless the A/B switch puts them back on the matrix-core kernel
-        c1 = cin == 1 and cout == 1 and not int(__import__("os").environ.get("HP_DCONV_C1_MFMA", "0") or 0)
+        c1 = cin == 1 and cout == 1 and not _DCONV_C1_MFMA
         nb = 0 if c1 else int(L.hp_dconv3_backward_data_workspace_bytes(b, cin, d, h, wd, rp))
         ws = torch.empty(nb // 4, dtype=torch.float32, device=x.device) if nb else None
         ge, we = _emu(g, prec, cin, cout), _emu(w, prec, cin, cout)
@@ -136,26 +101,22 @@ def _dconv3_grads(x, w, g, replicate, has_bias, need_dx, prec=0, w_param=None, b
     wprec = prec if _DCONV_WGRAD_BF16 else 0
     emu_w = wprec == 2 and cin > 1 and wd % 4 == 0   # the layers the bf16 weight-gradient kernel takes (others run exact)
     xe, ge = (x.bfloat16().float(), g.bfloat16().float()) if emu_w else (x, g)
-    # The weight gradient has no reader before the optimizer: second stream, as the regressor's (see _conv_grads for the
-    # allocation / lifetime rules: outputs allocated here on the main stream and not held, operands held until the main stream has
-    # waited for the kernel).  Only the plain case: leaf parameters without hooks whose .grad autograd will simply adopt.
-    side = _wgrad_side_stream(x.device) if (_DCONV_WGRAD_STREAM and w_param is not None) else None
-    if side is not None:
-        ps = [w_param] + ([b_param] if b_param is not None else [])
-        if any((not q.is_leaf) or q.grad is not None or getattr(q, "_backward_hooks", None) or
-               getattr(q, "_post_accumulate_grad_hooks", None) for q in ps):
-            side = None
+
+    def wgrad(stream):
+        _lib.check(L.hp_dconv3_backward_weight_p(xe.data_ptr(), ge.data_ptr(), dw.data_ptr(), _lib.ptr(db), b, cin, cout,
+                                                 d, h, wd, rp, wprec & 1, wsw.data_ptr(), stream), "hp_dconv3_backward_weight_p")
+
+    # The weight gradient has no reader before the optimizer: second stream, as the regressor's (_side_stream has the allocation
+    # and lifetime rules: dw and db are allocated above, on the main stream, and not held; the operands are).  Only the plain
+    # case: leaf parameters without hooks or accumulated gradients, whose .grad autograd will simply adopt.
+    side = None
+    if _WGRAD_ASYNC and _DCONV_WGRAD_STREAM and not force_main and _side.adoptable([w] + ([bias] if has_bias else []), False):
+        side = _side.stream(x.device)
     if side is None:
-        _lib.check(L.hp_dconv3_backward_weight_p(xe.data_ptr(), ge.data_ptr(), dw.data_ptr(), _lib.ptr(db), b, cin, cout,
-                                                 d, h, wd, rp, wprec & 1, wsw.data_ptr(), st), "hp_dconv3_backward_weight_p")
-        return gx, dw, db
-    main = torch.cuda.current_stream(x.device)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        _lib.check(L.hp_dconv3_backward_weight_p(xe.data_ptr(), ge.data_ptr(), dw.data_ptr(), _lib.ptr(db), b, cin, cout,
-                                                 d, h, wd, rp, wprec & 1, wsw.data_ptr(), _stream(x)), "hp_dconv3_backward_weight_p")
-    _hold(x.device, side, main, (xe, ge, wsw))
-    _side_dconv_calls[0] += 1
+        wgrad(st)
+    else:
+        _side.launch(x.device, side, wgrad, (xe, ge, wsw))
+        _side_dconv_calls[0] += 1
     return gx, dw, db
 
 
@@ -185,7 +146,7 @@ class _DConv3(torch.autograd.Function):
         ctx.cfg = (replicate, bias is not None, res is not None, float(slope))
         ctx.prec = _DCONV_PRECISION
         ctx.bias_ref = bias     # (the parameter itself, for the side-stream test of its backward; not a saved tensor: no version check)
-        ctx.use_epoch = _use_epoch[0]
+        _side.register(ctx, {1: w, 2: bias})
         return y
 
     @staticmethod
@@ -202,8 +163,8 @@ class _DConv3(torch.autograd.Function):
             x, w = ctx.saved_tensors
             g = gy
         with torch.cuda.device(x.device):
-            gx, dw, db = _dconv3_grads(x, w, g, replicate, has_bias, ctx.needs_input_grad[0], ctx.prec,
-                                       None if _shared_use(ctx, w) else w, ctx.bias_ref)
+            gx, dw, db = _dconv3_grads(x, w, g, replicate, ctx.bias_ref, ctx.needs_input_grad[0], ctx.prec,
+                                       _side.release(ctx, w, ctx.bias_ref))
         return gx, dw, db, None, (g if has_res else None), None
 
 
@@ -243,7 +204,7 @@ class _ConvGnRelu(torch.autograd.Function):
         ctx.cfg = (groups, bias is not None)
         ctx.prec = _DCONV_PRECISION
         ctx.bias_ref = bias
-        ctx.use_epoch = _use_epoch[0]
+        _side.register(ctx, {1: w, 2: bias})
         return y
 
     @staticmethod
@@ -263,8 +224,8 @@ class _ConvGnRelu(torch.autograd.Function):
                                                        gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), aff[0].data_ptr(),
                                                        aff[1].data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(),
                                                        _stream(z)), "hp_groupnorm_relu_backward_v2")
-            gx, dw, db = _dconv3_grads(x, w, dz, False, has_bias, ctx.needs_input_grad[0], ctx.prec,
-                                       None if _shared_use(ctx, w) else w, ctx.bias_ref)
+            gx, dw, db = _dconv3_grads(x, w, dz, False, ctx.bias_ref, ctx.needs_input_grad[0], ctx.prec,
+                                       _side.release(ctx, w, ctx.bias_ref))
         return gx, dw, db, dgamma, dbeta, None, None, None
 
 
@@ -272,7 +233,6 @@ class _ConvGnRelu(torch.autograd.Function):
 def conv3d_reppad(x, w, b, stride=1, residual=None, slope=1.0):
     """ReplicationPad3d(1) + Conv3d(3^3) [+ residual] [+ LeakyReLU(slope)] in one kernel."""
     assert stride == 1, "same-size convolution only; the strided entry of FeatureExtraction is `fe_entry`"
-    _note_use(w)
     return _DConv3.apply(x, w, b, True, residual, slope)
 
 
@@ -318,7 +278,6 @@ def feature_extraction_fused(x, fe):
     _need_cuda(x, "feature_extraction")
     a = conv3d_reppad(x, fe.conv1[1].weight, fe.conv1[1].bias)
     a = fe.conv1[3](fe.conv1[2](a))
-    _note_use(fe.weights)
     return _DConv3.apply(x, fe.weights, None, False, a, 1.0)   # box filter branch + learned branch, added in the epilogue
 
 
@@ -685,7 +644,6 @@ def conv3d(x, w, b=None, stride=1, padding=0):
 
 
 def conv3_gn_relu(x, w, b, gw, gb, groups, eps, out=None):
-    _note_use(w)
     return _ConvGnRelu.apply(x, w, b, gw, gb, groups, eps, out)
 
 
@@ -859,11 +817,11 @@ _res_bn_pending = [None]
 # are worth -8.1 ms/step, but its consumers are the 1^3 data gradients with 4 x planes output channels, which are HBM-bound on
 # exactly that output, and the extra read of z_a (as large as the output) costs them +8.3 ms: 472.3 ms with it, 468.4 without
 # (bn1 / bn2 hand-overs alone; 474.0 with neither).
-_BN_FUSE_RES = __import__("os").environ.get("HP_BN_FUSE_RES", "0") != "0"
+_BN_FUSE_RES = _lib.env_flag("HP_BN_FUSE_RES", False)
 
 
 def offer_res_bn(y, link) -> None:
-    _res_bn_pending[0] = None if (link is None or not _BN_FUSE_RES) else (__import__("weakref").ref(y), link)
+    _res_bn_pending[0] = None if (link is None or not _BN_FUSE_RES) else (weakref.ref(y), link)
 
 
 def take_res_bn(x):
@@ -871,7 +829,7 @@ def take_res_bn(x):
     return p[1] if (p is not None and p[0]() is x) else None
 
 
-_BN_FUSE = __import__("os").environ.get("HP_BN_FUSE", "1") != "0"
+_BN_FUSE = _lib.env_flag("HP_BN_FUSE", True)
 _bn_fused_calls = [0]   # data gradients that took a BatchNorm unit's sums (tests assert the path was taken where it should be)
 
 
@@ -886,20 +844,9 @@ def bn_link():
 # BatchNorm passes of backward's critical path overlap matrix-core work.  With two kernels in flight a kernel's duration
 # describes a contended launch, so bench.py times the step with the overlap and takes its per-kernel table / roofline from
 # appended steps with the mode switched off.
-_WGRAD_ASYNC = bool(int(__import__("os").environ.get("HP_WGRAD_STREAM", "1")))
-_WGRAD_SIDE_MODE = int(__import__("os").environ.get("HP_WGRAD_SIDE_MODE", "3"))
-_WGRAD_SIDE_MB = int(__import__("os").environ.get("HP_WGRAD_SIDE_MB", "512"))
-_side_streams = {}
-_joined_task = [-1]
-# Which top-level forward a weight's use count belongs to: `begin_forward()` (called by the regressor's forward) opens a new
-# epoch, so a count left behind by a forward whose backward never ran (validation without no_grad, an exception, a discarded
-# graph) cannot keep a weight off the side stream for the rest of the process; a backward that finds a count from another
-# epoch takes the main stream (always safe).
-_use_epoch = [0]
-
-
-def begin_forward() -> None:
-    _use_epoch[0] += 1
+_WGRAD_ASYNC = _lib.env_flag("HP_WGRAD_STREAM", True)
+_WGRAD_SIDE_MODE = _lib.env_int("HP_WGRAD_SIDE_MODE", 3)
+_WGRAD_SIDE_MB = _lib.env_int("HP_WGRAD_SIDE_MB", 512)
 
 
 def set_wgrad_async(on: bool) -> bool:
@@ -908,56 +855,9 @@ def set_wgrad_async(on: bool) -> bool:
     return prev
 
 
-def _wgrad_side_stream(device):
-    # only inside a backward pass: the join below is queued as an end-of-backward callback of that pass
-    if not _WGRAD_ASYNC or torch._C._current_graph_task_id() == -1:
-        return None
-    s = _side_streams.get(device)
-    if s is None:
-        # Same priority as the training stream.  HIP offers two levels on this device (priority_range() = (0, -1)); giving the
-        # training stream -- backward's critical path -- the high one, or the weight gradients the high one, measured 455.5 /
-        # 455.2 ms against 456.6 (HP_MAIN_PRIO in bench.py, HP_WGRAD_PRIO here: A/B hooks): inside the noise
-        s = _side_streams[device] = torch.cuda.Stream(device, priority=int(__import__("os").environ.get("HP_WGRAD_PRIO", "0")))
-    task = torch._C._current_graph_task_id()
-    if _joined_task[0] != task:
-        _joined_task[0] = task
-        torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
-    return s
-
-
-# Operands of weight gradients still queued on a side stream: (event recorded behind the kernel, tensors).  The tensors stay
-# referenced here -- NOT handed to the allocator with record_stream(): a record_stream'ed block is reusable only once the
-# HOST has seen its event complete, and in a training loop the host runs a whole step ahead of the device, so those blocks
-# were never reusable in time, the pool grew until allocation failed and every step paid for the allocator's
-# free-everything-and-synchronize path (measured: 1.2 s instead of 0.47 s per headline step with no host synchronisation
-# between steps).  Instead the MAIN stream waits for the weight gradient of `_HOLD_DEPTH` convolutions ago (a device-side
-# wait, normally already satisfied: the side stream runs one or two kernels behind) and only then is the reference dropped,
-# so the block returns to the allocator as an ordinary main-stream block, in stream order, and at most `_HOLD_DEPTH`
-# convolutions' operands are held beyond their autograd lifetime.
-_held = {}
-_HOLD_DEPTH = int(__import__("os").environ.get("HP_WGRAD_HOLD", "4"))
-
-
-def _hold(device, side, main, tensors):
-    q = _held.get(device)
-    if q is None:
-        q = _held[device] = __import__("collections").deque()
-    ev = torch.cuda.Event()
-    ev.record(side)
-    q.append((ev, tensors))
-    while len(q) > _HOLD_DEPTH:
-        ev0, _ = q.popleft()
-        main.wait_event(ev0)     # whatever reuses those blocks on the main stream is ordered behind the kernel that read them
-
-
-def join_side_streams():
-    """The current stream of every device waits for the weight gradients queued on its side stream.  Runs by itself
-    when the backward pass that queued them ends, i.e. before `backward()` returns to the caller."""
-    for dev, s in _side_streams.items():
-        torch.cuda.current_stream(dev).wait_stream(s)
-        q = _held.get(dev)
-        if q:
-            q.clear()            # everything queued so far is ordered before whatever the main stream does next
+# the mechanism is _side_stream's; these two names are what data_parallel.py and callers outside the package know
+_side_grad_listeners = _side.listeners
+join_side_streams = _side.join
 
 
 def _conv_grads(desc, x, w, dz, need_dx, addend=None, addend_mask=None, bn_in=None, force_main=False):
@@ -997,7 +897,8 @@ def _conv_grads(desc, x, w, dz, need_dx, addend=None, addend_mask=None, bn_in=No
                        "hp_conv3d_backward_data")
     desc.io &= ~HP_IO_W
     n = int(L.hp_conv3d_packed_weight_elems(_C.byref(desc)))
-    side = _wgrad_side_stream(x.device)
+    # force_main: the answer of _side.release (a weight used more than once in the graphs being differentiated)
+    side = _side.stream(x.device) if (_WGRAD_ASYNC and not force_main) else None
     if side is not None and _WGRAD_SIDE_MODE != 1:
         # Which weight gradients take the second stream (HP_WGRAD_SIDE_MODE; 1 = all of them: rounds 3-4): the convolutions WITH
         # taps (k > 1) -- their weight gradients are matrix-core-bound and re-read their operands through L2, so the memory-bound
@@ -1009,62 +910,40 @@ def _conv_grads(desc, x, w, dz, need_dx, addend=None, addend_mask=None, bn_in=No
         big = (x.numel() * x.element_size() + dz.numel() * dz.element_size()) >= (_WGRAD_SIDE_MB << 20)
         if desc.k == 1 and (_WGRAD_SIDE_MODE == 2 or big):
             side = None
-    if side is not None:
-        # The side-stream hand-over is safe only where nothing reads `dw` on the main stream before the join: a leaf whose
-        # gradient autograd merely adopts (or that we accumulate ourselves, below).  A tensor hook receives the gradient, a
-        # post-accumulate hook may read it (unless the gradient is pre-allocated, which is the accumulate path below), and a
-        # weight used twice in one graph has its two gradients SUMMED by autograd on the main stream: main-stream path.
-        hooked = bool(getattr(w, "_backward_hooks", None)) or \
-            (bool(getattr(w, "_post_accumulate_grad_hooks", None)) and not (w.is_leaf and w.grad is not None))
-        if (not w.is_leaf) or hooked or force_main:
-            side = None
-    if side is None:
-        dwp = torch.empty(n, dtype=torch.float32, device=x.device)
-        _lib.check(L.hp_conv3d_backward_weight(_C.byref(desc), x.data_ptr(), dz.data_ptr(), dwp.data_ptr(), st),
-                   "hp_conv3d_backward_weight")
-        if _same_as_packed(desc):
-            return dx, dwp.view_as(w)
-        dw = torch.empty_like(w)
-        _lib.check(L.hp_conv3d_unpack_wgrad(_C.byref(desc), dwp.data_ptr(), dw.data_ptr(), st), "hp_conv3d_unpack_wgrad")
-        return dx, dw
-    # The weight gradient has no consumer before the optimizer: it runs on a second stream, concurrently with the
-    # rest of backward on the main one (join_side_streams() before the first reader of the gradients).  Its output is
-    # allocated HERE, on the main stream (written on the side stream, read and freed on the main one after the join), and its
-    # operands are kept alive by _hold(): no block of this exchange is owned by, or recorded on, the side stream.
-    main = torch.cuda.current_stream(x.device)
-    accumulate = w.is_leaf and w.grad is not None
+    if side is not None and not _side.adoptable([w], True):
+        side = None
+    # `w.grad` already holds something (gradient accumulation over micro-batches, zero_grad(set_to_none=False), or a view into
+    # a GradBucketReducer bucket): autograd's AccumulateGrad would read `dw` on the MAIN stream before the side stream has
+    # written it.  The sum is therefore taken on the side stream, and autograd gets no gradient for this weight; whoever
+    # listens for gradients (the bucket reducer) is told directly.
+    accumulate = side is not None and w.grad is not None
     dwp = torch.empty(n, dtype=torch.float32, device=x.device)
     dw = dwp.view_as(w) if _same_as_packed(desc) else torch.empty_like(w)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        sst = _stream(x)
-        _lib.check(L.hp_conv3d_backward_weight(_C.byref(desc), x.data_ptr(), dz.data_ptr(), dwp.data_ptr(), sst),
+
+    def wgrad(stream):
+        _lib.check(L.hp_conv3d_backward_weight(_C.byref(desc), x.data_ptr(), dz.data_ptr(), dwp.data_ptr(), stream),
                    "hp_conv3d_backward_weight")
         if not _same_as_packed(desc):
-            _lib.check(L.hp_conv3d_unpack_wgrad(_C.byref(desc), dwp.data_ptr(), dw.data_ptr(), sst), "hp_conv3d_unpack_wgrad")
+            _lib.check(L.hp_conv3d_unpack_wgrad(_C.byref(desc), dwp.data_ptr(), dw.data_ptr(), stream), "hp_conv3d_unpack_wgrad")
         if accumulate:
-            # `w.grad` already holds something (gradient accumulation over micro-batches, zero_grad(set_to_none=False),
-            # or a view into a GradBucketReducer bucket): autograd's AccumulateGrad would read `dw` on the MAIN stream
-            # before the side stream has written it.  The sum is therefore taken here, on the side stream, and autograd
-            # gets no gradient for this weight; whoever listens for gradients (the bucket reducer) is told directly.
             with torch.no_grad():
                 w.grad.add_(dw)
-    # (a dw that goes to autograd must NOT be held: autograd adopts a gradient tensor as `w.grad` only while nobody else
-    # references it, and would otherwise clone it -- on the main stream, before the side stream has written it.  A dw that was
-    # summed into w.grad above dies with this call and MUST be held: its block was allocated on the main stream.)
+
+    if side is None:
+        wgrad(st)
+        return dx, dw
+    # The weight gradient has no consumer before the optimizer: it runs on the second stream, concurrently with the rest of
+    # backward on the main one (_side_stream has the two ownership rules).  A dw that goes to autograd must NOT be held, and
+    # nothing here may still reference it when autograd looks; a dw that was summed into w.grad dies with this call and MUST be.
     keep = (x, dz, w, dwp, dw) if accumulate else ((x, dz, w) if dw.data_ptr() == dwp.data_ptr() else (x, dz, w, dwp))
-    _hold(x.device, side, main, keep)
+    _side.launch(x.device, side, wgrad, keep)
     _side_conv_calls[0] += 1
-    del dwp, keep
+    del dwp, keep, wgrad
     if accumulate:
         for fn in _side_grad_listeners:   # called with the MAIN stream current: a listener orders itself behind both
             fn(w, side)
         return dx, None
     return dx, dw
-
-
-# callables (parameter, side_stream) run after a weight gradient was ACCUMULATED on the side stream (see above)
-_side_grad_listeners = []
 
 
 class _ConvBnAct(torch.autograd.Function):
@@ -1075,7 +954,7 @@ class _ConvBnAct(torch.autograd.Function):
                 bn_in=None, bn_out=None):
         L = _lib.lib()
         x = x.contiguous()
-        ctx.use_epoch = _use_epoch[0]   # (the use count of w itself: _note_use() in the wrappers conv_bn_act / deconv_bn_relu)
+        _side.register(ctx, {1: w})
         cout = w.shape[1] if transposed else w.shape[0]
         desc = _desc(x, cout, k, stride, pad, transposed)
         do, ho, wo = _out_dims(desc)
@@ -1210,7 +1089,7 @@ class _ConvBnAct(torch.autograd.Function):
                 addend, addend_mask, last = link_in.take()
             # (a block input reaches two convolutions: its gradient is complete only in the one that runs last)
             dx, dw = _conv_grads(desc, x, w, dz, ctx.needs_input_grad[0], addend, addend_mask, bn_in=ctx.bn_links[0] if last else None,
-                                 force_main=_WGRAD_ASYNC and _shared_use(ctx, w))
+                                 force_main=_side.release(ctx, w))
             if not last:           # first of two convolutions reading the block input: park the partial sum
                 link_in.g, dx = dx, None
             gres = g
@@ -1232,6 +1111,7 @@ class _ConvBiasToNCDHW(torch.autograd.Function):
         L = _lib.lib()
         x = x.contiguous()
         ctx.bn_in = bn_in
+        _side.register(ctx, {1: w})
         cout = w.shape[0]
         desc = _desc(x, cout, 1, 1, 0, False)
         st = _stream(x)
@@ -1262,7 +1142,8 @@ class _ConvBiasToNCDHW(torch.autograd.Function):
             dycl = torch.empty(b, d, h, wd_, c, dtype=torch.float32, device=x.device)
             _lib.check(L.hp_layout_transpose(dy.data_ptr(), dycl.data_ptr(), b, d * h * wd_, c, 0, st),
                        "hp_layout_transpose")
-            dx, dw = _conv_grads(desc, x, w, dycl, ctx.needs_input_grad[0], bn_in=ctx.bn_in)
+            dx, dw = _conv_grads(desc, x, w, dycl, ctx.needs_input_grad[0], bn_in=ctx.bn_in,
+                                 force_main=_side.release(ctx, w))
             dbias = dy.sum(dim=(0, 2, 3, 4))
         return dx, dw, dbias, None
 
@@ -1293,15 +1174,11 @@ class _MaxPool3CL(torch.autograd.Function):
 
 def conv_bn_act(x, conv, bn, relu=True, residual=None, link_in=None, link_out=None, res_link=None, bn_in=None, bn_out=None):
     """x channels-last (B,D,H,W,C).  bn_in / bn_out: BnLinks to the unit that produced x / to the one consumer of the output."""
-    if _WGRAD_ASYNC:
-        _note_use(conv.weight)
     return _ConvBnAct.apply(x, conv.weight, bn.weight, bn.bias, residual, bn, conv.kernel_size[0], conv.stride[0],
                             conv.padding[0], False, relu, link_in, link_out, res_link, bn_in, bn_out)
 
 
 def deconv_bn_relu(x, deconv, bn, bn_in=None, bn_out=None):
-    if _WGRAD_ASYNC:
-        _note_use(deconv.weight)
     return _ConvBnAct.apply(x, deconv.weight, bn.weight, bn.bias, None, bn, 4, 2, 1, True, True, None, None, None, bn_in, bn_out)
 
 
@@ -1313,6 +1190,7 @@ class _StemConvBnReluPool(torch.autograd.Function):
     def forward(ctx, x, w, gamma, beta, bn):
         L = _lib.lib()
         x = x.contiguous()
+        _side.register(ctx, {1: w})
         cout = w.shape[0]
         desc = _desc(x, cout, 7, 1, 3, False)
         b, d, h, wd_, _ = x.shape
@@ -1369,7 +1247,7 @@ class _StemConvBnReluPool(torch.autograd.Function):
                                                        cout, mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                                                        1 if train else 0, dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), st),
                        "hp_stem_bn_relu_pool_backward")
-            dx, dw = _conv_grads(desc, x, w, dz, ctx.needs_input_grad[0])
+            dx, dw = _conv_grads(desc, x, w, dz, ctx.needs_input_grad[0], force_main=_side.release(ctx, w))
         return dx, dw, dgamma, dbeta, None
 
 

@@ -595,8 +595,8 @@ def test_side_stream_weight_gradient_with_a_tensor_hook_or_shared_weight():
 
 
 def test_a_convolution_weight_used_twice_in_one_graph_stays_on_the_main_stream():
-    """The shared-weight rule without a hook in play (round 4: the use counts are taken by the wrappers conv_bn_act /
-    deconv_bn_relu, where grad mode is the caller's -- inside Function.forward it is always off, so the counts of rounds 3-4 never
+    """The shared-weight rule without a hook in play (every Function registers its use in `forward`, where `ctx.needs_input_grad`
+    speaks for the caller's grad mode -- `torch.is_grad_enabled()` is always off there, so the counts of rounds 3-4 never
     counted): the same Conv3d twice in one graph -> autograd SUMS the two weight gradients on the main stream, so neither may be
     written on the second stream; a weight used once takes it.  Gradients equal the one-stream run."""
     from torch import nn
@@ -626,6 +626,81 @@ def test_a_convolution_weight_used_twice_in_one_graph_stays_on_the_main_stream()
         (g1, n1), (g0, n0_) = run(True, twice), run(False, twice)
         assert n0_ == 0 and n1 == (0 if twice else 1), (twice, n1, n0_)
         assert rel_l2(g1.cpu().numpy(), g0.cpu().numpy()) < 1e-5
+
+
+@pytest.mark.parametrize("unit", ["stem", "head"])
+def test_a_stem_or_head_weight_used_twice_stays_on_the_main_stream(unit):
+    """The same rule for the two units that have no wrapper-side bookkeeping of their own (every Function registers its use in
+    `forward`, _side_stream.register): the stem convolution (ragged W = 6) and the head's 256 -> 24 convolution with bias, each
+    applied to two inputs in one graph, keep both weight gradients on the main stream; used once they take the second one."""
+    from torch import nn
+
+    g = torch.Generator().manual_seed(23)
+    if unit == "stem":
+        xs = [torch.randn(1, 1, 6, 4, 6, generator=g).cuda() for _ in range(2)]
+        w0, b0 = (torch.randn(64, 1, 7, 7, 7, generator=g) * 0.05).cuda(), None
+    else:
+        xs = [torch.randn(1, 4, 4, 8, 256, generator=g).cuda() for _ in range(2)]
+        w0, b0 = (torch.randn(24, 256, 1, 1, 1, generator=g) * 0.05).cuda(), torch.randn(24, generator=g).cuda()
+
+    def run(async_on, twice):
+        if unit == "stem":
+            conv, bn = nn.Conv3d(1, 64, 7, padding=3, bias=False).cuda(), nn.BatchNorm3d(64).cuda()
+
+            def f(x):
+                return ops.stem_conv_bn_relu_pool(x, conv, bn)
+        else:
+            conv = nn.Conv3d(256, 24, 1).cuda()
+
+            def f(x):
+                return ops.head_conv_to_ncdhw(x, conv)
+        with torch.no_grad():
+            conv.weight.copy_(w0)
+            if b0 is not None:
+                conv.bias.copy_(b0)
+        prev = ops.set_wgrad_async(async_on)
+        n0 = ops._side_conv_calls[0]
+        try:
+            y = f(xs[0])
+            if twice:
+                y = y + f(xs[1])
+            y.square().mean().backward()
+            torch.cuda.synchronize()
+        finally:
+            ops.set_wgrad_async(prev)
+        assert not getattr(conv.weight, "_hp_uses", {}) and not getattr(conv.weight, "_hp_shared", False)
+        return conv.weight.grad.clone(), ops._side_conv_calls[0] - n0
+
+    for twice in (True, False):
+        (g1, n1), (g0, n0_) = run(True, twice), run(False, twice)
+        assert n0_ == 0 and n1 == (0 if twice else 1), (twice, n1, n0_)
+        assert rel_l2(g1.cpu().numpy(), g0.cpu().numpy()) < 1e-5
+
+
+def test_the_regressors_side_stream_schedule():
+    """Which weight gradients of one posenet3d_50 training step take the second stream (the shape of
+    test_weight_gradients_on_side_stream_match_serial): every weight is used once, so where the use is registered must not move
+    any of them.  (The thin-channel counterpart, 2 launches for its two layers, is pinned by
+    test_dconv_gpu.py::test_thin_channel_weight_gradients_on_the_second_stream_equal_the_serial_ones.)"""
+    from hiddenpose_amd.posenet3d_50 import get_pose_net_50
+
+    net = get_pose_net_50()
+    hpt.fill_module(net, "pose_net.")
+    net = net.cuda().train()
+    x = (hpt.synthetic_meas(2, 32, 32, "uniform", seed=105) * 10.0).cuda()
+    prev = ops.set_wgrad_async(True)
+    try:
+        for _ in range(2):      # the second step finds every use of the first one released
+            net.zero_grad(set_to_none=True)
+            n0 = ops._side_conv_calls[0]
+            y = net(x)
+            (y * y).mean().backward()
+            # 57 = all of the net's convolutions (operands this small pass the size rule of _conv_grads).  MEASURED on the commit
+            # before the uses moved into Function.forward (use counts by forward epoch), not on the code under test.
+            assert ops._side_conv_calls[0] - n0 == 57
+    finally:
+        ops.set_wgrad_async(prev)
+    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("ca,cb,kb,transposed,dims", [

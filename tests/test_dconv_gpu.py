@@ -216,7 +216,7 @@ def test_thin_channel_weight_gradients_on_the_second_stream_equal_the_serial_one
 @pytest.mark.gpu
 def test_a_thin_channel_weight_used_twice_stays_on_the_main_stream():
     """A weight that appears twice in one graph has its two gradients SUMMED by autograd on the main stream: neither may be written
-    on the second stream (hip_ops._count_use / _shared_use, as for the regressor's convolutions).  Bit-equal to the one-stream run,
+    on the second stream (_side_stream.register / release, as for the regressor's convolutions).  Bit-equal to the one-stream run,
     over two passes (the use counts return to zero)."""
     g = torch.Generator().manual_seed(78)
     x = torch.randn(1, 4, 10, 16, 64, generator=g).cuda()
