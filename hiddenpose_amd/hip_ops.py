@@ -9,8 +9,8 @@ HIP device.  With HP_OPTIMIZER_IMPL=hip the optimizer is hiddenpose_amd.optimize
 """
 from __future__ import annotations
 
+import collections
 import os
-import weakref
 
 import torch
 import torch.nn.functional as F
@@ -34,6 +34,7 @@ def _need_cuda(x: torch.Tensor, what: str) -> None:
 # ---------------------------------------------------------------- thin-channel 3^3 convolutions
 import ctypes as _C
 
+from . import _block_links as _links
 from . import _lib
 from . import _side_stream as _side
 
@@ -751,91 +752,22 @@ def _pack(desc, w, want_fwd, want_dgrad, half=False):
         desc.io = io0
 
 
-class GradLink:
-    """Carries one gradient contribution to a tensor that is used twice inside a Bottleneck (block input:
-    conv1 + identity shortcut, or conv1 + shortcut convolution) from the autograd node that produces it
-    first to the data-gradient GEMM that runs last, which adds it in its epilogue.  Replaces the
-    separate accumulation pass autograd would issue."""
-    __slots__ = ("g", "arrivals", "mask")
+# The hand-overs between the units' autograd nodes (what they carry, and when a take is refused): _block_links
+GradLink, ResLink, BnLink = _links.GradLink, _links.ResLink, _links.BnLink
+offer_res_bn, take_res_bn = _links.offer, _links.take_offer
 
-    def __init__(self):
-        self.g = None
-        self.arrivals = 0
-        self.mask = None   # byte mask gating `g` (identity shortcut: g is the block's raw output gradient)
-
-    def take(self):
-        """One consumer of the block input runs its backward: returns (addend, mask, last).  The link is consumed
-        by ONE backward pass over the graph; a second pass (retain_graph=True, torch.autograd.grad twice) would
-        silently drop the parked partial sums, so it raises instead."""
-        if self.arrivals <= 0:
-            raise RuntimeError("hiddenpose_amd: a Bottleneck's fused gradient link was already consumed -- a second "
-                               "backward pass over the same graph (retain_graph=True) is not supported; run the "
-                               "forward again")
-        self.arrivals -= 1
-        addend, self.g = self.g, None
-        mask, self.mask = self.mask, None
-        return addend, mask, self.arrivals == 0
-
-
-class ResLink:
-    """Joins the shortcut unit (downsample conv + BN) of a Bottleneck to the unit that adds its output as the
-    residual.  The gradient of the residual branch is dy (.) [block output > 0]; instead of writing that product
-    the residual unit hands back dy itself and leaves the sign mask of its output here, and the shortcut unit's
-    BatchNorm backward applies the mask while it reads dy."""
-    __slots__ = ("mask", "affine", "short", "done")
-
-    def __init__(self):
-        self.mask = None
-        self.affine = None   # (mean, rstd, gamma, beta) of the shortcut's BatchNorm while its output is still raw
-        self.short = None    # (z, mean, rstd, gamma, train) of the shortcut unit: the residual unit's backward runs
-        self.done = None     # both BatchNorm backwards in one pair of passes and leaves (dz, dgamma, dbeta) here
-
-
-class BnLink:
-    """Joins a conv + BatchNorm (+ ReLU) unit WITHOUT residual (the producer) to the one convolution that consumes its output
-    (the consumer).  The consumer's data gradient IS the producer's incoming gradient, so the consumer's data-gradient kernel
-    also takes the producer's two BatchNorm-backward sums (hp_conv3d_backward_data_bnsums, from the tile in hand and one read
-    of the producer's raw output) and leaves them here; the producer's backward then skips its reduction pass over dy and z
-    (hp_bn_backward_presummed).  Exact-fp32 tensors and whole-tile geometries only; otherwise `sums` stays None and nothing
-    changes.  HP_BN_FUSE=0 switches the hand-over off (A/B runs)."""
-    __slots__ = ("src", "sums")
-
-    def __init__(self):
-        self.src = None    # (z, mean, rstd, gamma, beta, relu, byte mask or None) of the producer, set by its forward
-        self.sums = None   # HP_STATS_SLOTS x 2C doubles, set by the consumer's backward
-
-
-# A Bottleneck's OUTPUT unit (bn3 + identity shortcut + ReLU) is consumed by the next block: by its conv1 and by its identity
-# shortcut.  The block-output gradient is complete in the epilogue of that conv1's data gradient (it adds the parked shortcut
-# gradient), so conv1 of the NEXT block is the consumer of this unit's BnLink.  The two forwards do not see each other (blocks
-# sit in an nn.Sequential): the producer offers its link together with a weak reference to its output tensor, and the next
-# block takes it if -- and only if -- its input IS that tensor.
-_res_bn_pending = [None]
-
-
-# OFF by default (HP_BN_FUSE_RES=1 turns it on): measured at the headline shape, same box -- the reduction passes it removes
-# are worth -8.1 ms/step, but its consumers are the 1^3 data gradients with 4 x planes output channels, which are HBM-bound on
-# exactly that output, and the extra read of z_a (as large as the output) costs them +8.3 ms: 472.3 ms with it, 468.4 without
-# (bn1 / bn2 hand-overs alone; 474.0 with neither).
+_BN_FUSE = _lib.env_flag("HP_BN_FUSE", True)     # 0: BatchNorm-backward sums by the unit's own reduction pass (A/B runs)
+# The same hand-over for a Bottleneck's OUTPUT unit: OFF by default.  The reduction passes it removes are worth -8.1 ms/step at the
+# headline shape, but the extra read of z costs its consumers, the HBM-bound 1^3 data gradients, +8.3 ms (472.3 against 468.4).
 _BN_FUSE_RES = _lib.env_flag("HP_BN_FUSE_RES", False)
-
-
-def offer_res_bn(y, link) -> None:
-    _res_bn_pending[0] = None if (link is None or not _BN_FUSE_RES) else (weakref.ref(y), link)
-
-
-def take_res_bn(x):
-    p, _res_bn_pending[0] = _res_bn_pending[0], None
-    return p[1] if (p is not None and p[0]() is x) else None
-
-
-_BN_FUSE = _lib.env_flag("HP_BN_FUSE", True)
 _bn_fused_calls = [0]   # data gradients that took a BatchNorm unit's sums (tests assert the path was taken where it should be)
 
 
-def bn_link():
-    """A BnLink when a backward pass may follow and the hand-over is enabled, else None."""
-    return BnLink() if (_BN_FUSE and torch.is_grad_enabled()) else None
+def bn_link(block_output=False):
+    """A BnLink when a backward pass may follow and the hand-over is enabled (block_output: for a Bottleneck's output unit,
+    whose consumer is the next block's conv1), else None."""
+    on = _BN_FUSE and (_BN_FUSE_RES or not block_output)
+    return BnLink() if (on and torch.is_grad_enabled()) else None
 
 
 # Weight gradients on a second HIP stream (default since round 4; HP_WGRAD_STREAM=0 or set_wgrad_async(False) keeps
@@ -886,7 +818,7 @@ def _conv_grads(desc, x, w, dz, need_dx, addend=None, addend_mask=None, bn_in=No
                                                         gs.data_ptr(), bs.data_ptr(), 1 if relu_s else 0, _lib.ptr(mask_s),
                                                         sums.data_ptr(), _C.byref(fused), st), "hp_conv3d_backward_data_bnsums")
             if fused.value:
-                bn_in.sums = sums
+                bn_in.give_sums(sums, dx)   # valid for this dx only: the producer checks that it IS its incoming gradient
                 _bn_fused_calls[0] += 1
         elif addend_mask is not None:
             _lib.check(L.hp_conv3d_backward_data_masked(_C.byref(desc), dz.data_ptr(), wd.data_ptr(), dx.data_ptr(),
@@ -946,161 +878,174 @@ def _conv_grads(desc, x, w, dz, need_dx, addend=None, addend_mask=None, bn_in=No
     return dx, dw
 
 
+def _conv_bn_stats(desc, x, w, bn, act, st):
+    """z = conv(x, w) with BatchNorm's statistics reduced in its epilogue: (z, mean, rstd, train).  Training mode updates the
+    running statistics; act: z is stored as bf16."""
+    L = _lib.lib()
+    cout = desc.Cout
+    wh = _w_half(desc, _h(x), desc.Cin)
+    wf, _ = _pack(desc, w, True, False, wh)
+    z = torch.empty(desc.B, *_out_dims(desc), cout, dtype=_BF if act else torch.float32, device=x.device)
+    train = bn.training
+    stats = torch.empty(_lib.STATS_SLOTS * 2 * cout, dtype=torch.float64, device=x.device) if train else None
+    desc.io = (HP_IO_X if _h(x) else 0) | (HP_IO_W if wh else 0) | (HP_IO_Y if act else 0)
+    _lib.check(L.hp_conv3d_forward(_C.byref(desc), x.data_ptr(), wf.data_ptr(), None, z.data_ptr(), _lib.ptr(stats), st),
+               "hp_conv3d_forward")
+    mean = torch.empty(cout, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    if train:
+        mom = 0.1 if bn.momentum is None else bn.momentum
+        _lib.check(L.hp_bn_train_finalize_counted(stats.data_ptr(), z.numel() // cout, cout, bn.eps, mom, mean.data_ptr(),
+                                                  rstd.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                                                  bn.num_batches_tracked.data_ptr(), st), "hp_bn_train_finalize")
+    else:
+        _lib.check(L.hp_bn_eval_stats(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), cout, bn.eps,
+                                      mean.data_ptr(), rstd.data_ptr(), st), "hp_bn_eval_stats")
+    return z, mean, rstd, train
+
+
+# What a conv + BatchNorm unit is told besides its tensors: the module facts, then its links (_block_links).  grad_in: x is read by
+# a second node too, its gradient is summed there; grad_out: res is the block input, its gradient is parked there; res: between a
+# block's shortcut unit and its output unit; bn_in / bn_out: to the unit that produced x / to the ONE consumer of the output.
+_Unit = collections.namedtuple("_Unit", "bn k stride pad transposed relu grad_in grad_out res bn_in bn_out", defaults=(None,) * 5)
+
+# What a unit is inside its block.  The role decides the forward's tail and the BatchNorm-backward path (_bn_unit_backward).
+_PLAIN = "plain"                    # y = act(BN(conv(x)))
+_SHORTCUT = "shortcut"              # a block's shortcut convolution: hands on its RAW output, the output unit applies its BN
+_OUT_IDENTITY = "out+identity"      # a block's output unit, res = the block input
+_OUT_SHORTCUT = "out+shortcut"      # a block's output unit, res = the raw output of the block's shortcut unit
+_EXTERNAL_RES = "external res"      # y = act(BN(conv(x)) + res), res anybody's tensor: its gradient goes back to autograd
+
+
+def _role(u, res):
+    assert u.grad_out is None or u.res is None
+    if res is None:
+        assert u.grad_out is None and not (u.res is not None and u.relu), "a shortcut unit has no ReLU of its own"
+        return _PLAIN if u.res is None else _SHORTCUT
+    assert u.relu or (u.grad_out is None and u.res is None), "a block's output unit ends in a ReLU"
+    return _OUT_IDENTITY if u.grad_out is not None else _EXTERNAL_RES if u.res is None else _OUT_SHORTCUT
+
+
+def _bn_unit_backward(role, res_link, sums, dy, z, mask, mean, rstd, gamma, beta, relu, train, act, st):
+    """BatchNorm (+ ReLU, + residual) backward of one unit: (dz, dgamma, dbeta, g), g = the residual's gradient where it has to
+    be written out.  sums: this unit's two reduction sums if its consumer's data gradient took them (BnLink)."""
+    L = _lib.lib()
+    cout = z.shape[-1]
+    M = z.numel() // cout
+    hdt = _BF if act else torch.float32     # dz (to the convolution gradients) and g (to the residual input)
+    bio = (HP_BN_DY if _h(dy) else 0) | (HP_BN_DZ if act else 0) | (HP_BN_Z if _h(z) else 0)
+    if role == _SHORTCUT:
+        # no ReLU of its own: dy is the block's raw output gradient and still lacks the output unit's byte mask -- unless that
+        # unit has already run this BatchNorm's backward next to its own (dual pass below)
+        mask, done = res_link.take("mask"), res_link.take("done")
+        if done is not None:
+            return (*done, None)
+        relu = mask is not None
+    dz, dgamma, dbeta = torch.empty_like(z, dtype=hdt), torch.empty_like(gamma), torch.empty_like(gamma)
+    short = res_link.take("short") if (role == _OUT_SHORTCUT and cout <= 1024) else None
+    nws = (int(L.hp_bn_backward_workspace_bytes(cout)) + 15) // 16 * 16      # one unit's workspace; the dual pass: two
+    ws = torch.empty(nws // 4 + 2 if short is None else 2 * nws // 4 + 8, dtype=torch.float32, device=z.device)
+    if short is not None:
+        # both BatchNorm backwards of the block's end in one pair of passes; the shortcut unit finds its result in the link
+        zb, mb, rb, gb, trb = short
+        dzb, dgb, dbb = torch.empty_like(zb, dtype=hdt), torch.empty_like(gb), torch.empty_like(gb)
+        _lib.check(L.hp_bn_backward_dual(dy.data_ptr(), mask.data_ptr(), M, cout, z.data_ptr(), dz.data_ptr(),
+                                         mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), 1 if train else 0,
+                                         dgamma.data_ptr(), dbeta.data_ptr(), zb.data_ptr(), dzb.data_ptr(), mb.data_ptr(),
+                                         rb.data_ptr(), gb.data_ptr(), 1 if trb else 0, dgb.data_ptr(), dbb.data_ptr(),
+                                         ws.data_ptr(), bio, st), "hp_bn_backward_dual")
+        res_link.give("done", (dzb, dgb, dbb))
+        return dz, dgamma, dbeta, None
+    if sums is not None:    # coefficient kernel + apply pass only (gated by the byte mask the sums were taken with, if any)
+        _lib.check(L.hp_bn_backward_presummed(dy.data_ptr(), z.data_ptr(), dz.data_ptr(), M, cout, mean.data_ptr(),
+                                              rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1 if relu else 0,
+                                              1 if train else 0, dgamma.data_ptr(), dbeta.data_ptr(), _lib.ptr(mask),
+                                              sums.data_ptr(), ws.data_ptr(), bio, st), "hp_bn_backward_presummed")
+        return dz, dgamma, dbeta, None
+    # g = dy (.) [y > 0] for anybody's residual; inside a block its consumer is one of our nodes and takes dy and the byte mask
+    g = torch.empty_like(z, dtype=hdt) if role == _EXTERNAL_RES else None
+    _lib.check(L.hp_bn_backward(dy.data_ptr(), None, z.data_ptr(), _lib.ptr(g), dz.data_ptr(), M, cout,
+                                mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                1 if relu else 0, 1 if train else 0, dgamma.data_ptr(), dbeta.data_ptr(),
+                                _lib.ptr(mask), ws.data_ptr(), bio, st), "hp_bn_backward")
+    return dz, dgamma, dbeta, g
+
+
 class _ConvBnAct(torch.autograd.Function):
-    """y = act(BN(conv(x)) [+ res]) with the BN batch statistics reduced in the conv epilogue."""
+    """y = act(BN(conv(x)) [+ res]) with the BN batch statistics reduced in the conv epilogue.  u: the unit's _Unit."""
 
     @staticmethod
-    def forward(ctx, x, w, gamma, beta, res, bn, k, stride, pad, transposed, relu, link_in=None, link_out=None, res_link=None,
-                bn_in=None, bn_out=None):
+    def forward(ctx, x, w, gamma, beta, res, u):
         L = _lib.lib()
         x = x.contiguous()
         _side.register(ctx, {1: w})
-        cout = w.shape[1] if transposed else w.shape[0]
-        desc = _desc(x, cout, k, stride, pad, transposed)
-        do, ho, wo = _out_dims(desc)
+        desc = _desc(x, w.shape[1] if u.transposed else w.shape[0], u.k, u.stride, u.pad, u.transposed)
+        cout = desc.Cout
         st = _stream(x)
         act = _act_bf16 or _h(x)   # bf16 activation storage: z, y (and dz, dx in the backward) are bf16; statistics fp32
+        role = _role(u, res)
+        mask = None
         with torch.cuda.device(x.device):
-            wh = _w_half(desc, _h(x), desc.Cin)
-            wf, _ = _pack(desc, w, True, False, wh)
-            z = torch.empty(desc.B, do, ho, wo, cout, dtype=_BF if act else torch.float32, device=x.device)
+            z, mean, rstd, train = _conv_bn_stats(desc, x, w, u.bn, act, st)
             M = z.numel() // cout
-            train = bn.training
-            stats = torch.empty(_lib.STATS_SLOTS * 2 * cout, dtype=torch.float64, device=x.device) if train else None
-            desc.io = (HP_IO_X if _h(x) else 0) | (HP_IO_W if wh else 0) | (HP_IO_Y if act else 0)
-            _lib.check(L.hp_conv3d_forward(_C.byref(desc), x.data_ptr(), wf.data_ptr(), None, z.data_ptr(),
-                                           _lib.ptr(stats), st), "hp_conv3d_forward")
-            mean = torch.empty(cout, dtype=torch.float32, device=x.device)
-            rstd = torch.empty_like(mean)
-            if train:
-                mom = 0.1 if bn.momentum is None else bn.momentum
-                _lib.check(L.hp_bn_train_finalize_counted(stats.data_ptr(), M, cout, bn.eps, mom, mean.data_ptr(), rstd.data_ptr(),
-                                                          bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                                          bn.num_batches_tracked.data_ptr(), st), "hp_bn_train_finalize")
+            if role == _SHORTCUT:
+                u.res.give("affine", (mean, rstd, gamma, beta))
+                u.res.give("short", (z.detach(), mean, rstd, gamma, train))   # an alias, not the output object: no ctx cycle
+                y = z
             else:
-                _lib.check(L.hp_bn_eval_stats(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), cout, bn.eps,
-                                              mean.data_ptr(), rstd.data_ptr(), st), "hp_bn_eval_stats")
-            if res_link is not None and res is None and not relu:
-                # Shortcut unit of a Bottleneck: its BatchNorm is applied by the unit that adds it as the residual
-                # (hp_bn_apply_res_bn); the raw convolution output travels instead of a normalised copy.
-                res_link.affine = (mean, rstd, gamma, beta)
-                res_link.short = (z.detach(), mean, rstd, gamma, train)   # an alias, not the output object: no ctx cycle
-                ctx.save_for_backward(x, w, gamma, beta, z, None, mean, rstd)
-                ctx.cfg = (desc, relu, train, False)
-                ctx.act = _act_bf16 or _h(x)
-                ctx.links = (link_in, link_out, res_link)
-                ctx.bn_links = (bn_in, None)
-                return z
-            y = torch.empty_like(z, dtype=_BF if act else torch.float32)
-            bio = (HP_BN_ACT | HP_BN_Z) if act else 0
-            if res is not None:
-                res = res.contiguous()
-                assert (res_link is not None and res_link.affine is not None) or _h(res) == act, "residual / output element types differ"
-            # with a residual the backward needs the sign pattern of the output: a byte per channel quad, written here
-            mask = (torch.empty(M * cout // 4, dtype=torch.uint8, device=x.device)
-                    if (res is not None and relu and any(ctx.needs_input_grad)) else None)
-            raff = res_link.affine if (res_link is not None and res is not None) else None
-            if raff is not None:
-                res_link.affine = None
-                _lib.check(L.hp_bn_apply_res_bn(z.data_ptr(), res.data_ptr(), y.data_ptr(), M, cout, mean.data_ptr(),
-                                                rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1 if relu else 0,
-                                                _lib.ptr(mask), raff[0].data_ptr(), raff[1].data_ptr(), raff[2].data_ptr(),
-                                                raff[3].data_ptr(), bio, st), "hp_bn_apply_res_bn")
-            else:
-                _lib.check(L.hp_bn_apply(z.data_ptr(), _lib.ptr(res), y.data_ptr(), M, cout, mean.data_ptr(), rstd.data_ptr(),
-                                         gamma.data_ptr(), beta.data_ptr(), 1 if relu else 0, _lib.ptr(mask), bio, st), "hp_bn_apply")
-        # without a residual the mask is rebuilt from z; y itself is kept only by the consumer that reads it as input
-        ctx.save_for_backward(x, w, gamma, beta, z, mask, mean, rstd)
-        ctx.cfg = (desc, relu, train, res is not None)
-        ctx.act = act
-        ctx.links = (link_in, link_out, res_link)
-        ctx.bn_links = (bn_in, None)
-        if bn_out is not None and not act and train and res_link is None:
-            if res is None and link_out is None:
-                # producer of a BnLink: a plain fp32 unit in training mode whose output gradient arrives from ONE data gradient
-                bn_out.src = (z.detach(), mean, rstd, gamma.detach(), beta.detach(), relu, None)
-                ctx.bn_links = (bn_in, bn_out)
-            elif res is not None and relu and mask is not None and raff is None:
-                # a block's output unit with an identity shortcut: the mask is the byte mask of the output (see offer_res_bn)
-                bn_out.src = (z.detach(), mean, rstd, gamma.detach(), beta.detach(), True, mask)
-                ctx.bn_links = (bn_in, bn_out)
+                y = torch.empty_like(z)
+                bio = (HP_BN_ACT | HP_BN_Z) if act else 0
+                if res is not None:
+                    res = res.contiguous()
+                    # the backward needs the output's sign pattern, a byte per channel quad (without a residual: rebuilt from z)
+                    if u.relu and any(ctx.needs_input_grad):
+                        mask = torch.empty(M * cout // 4, dtype=torch.uint8, device=x.device)
+                if role == _OUT_SHORTCUT:
+                    raff = u.res.take("affine")
+                    assert raff is not None, "the block's shortcut unit has not run"
+                    _lib.check(L.hp_bn_apply_res_bn(z.data_ptr(), res.data_ptr(), y.data_ptr(), M, cout, mean.data_ptr(),
+                                                    rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1 if u.relu else 0,
+                                                    _lib.ptr(mask), raff[0].data_ptr(), raff[1].data_ptr(), raff[2].data_ptr(),
+                                                    raff[3].data_ptr(), bio, st), "hp_bn_apply_res_bn")
+                else:
+                    assert res is None or _h(res) == act, "residual / output element types differ"
+                    _lib.check(L.hp_bn_apply(z.data_ptr(), _lib.ptr(res), y.data_ptr(), M, cout, mean.data_ptr(), rstd.data_ptr(),
+                                             gamma.data_ptr(), beta.data_ptr(), 1 if u.relu else 0, _lib.ptr(mask), bio, st),
+                               "hp_bn_apply")
+        ctx.save_for_backward(x, w, gamma, beta, z, mask, mean, rstd)   # y is kept only by the consumer that reads it as input
+        ctx.cfg, ctx.role, ctx.bn_out = (desc, train, act, u), role, None
+        # producer of a BnLink: an fp32 unit in training mode whose output gradient arrives from ONE data gradient -- a plain
+        # unit, or a block's output unit with an identity shortcut (complete in the next block's conv1: _block_links.offer)
+        if u.bn_out is not None and train and not act and (role == _PLAIN or (role == _OUT_IDENTITY and mask is not None)):
+            u.bn_out.src = (z.detach(), mean, rstd, gamma.detach(), beta.detach(), u.relu, mask)
+            ctx.bn_out = u.bn_out
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        L = _lib.lib()
         x, w, gamma, beta, z, mask, mean, rstd = ctx.saved_tensors
-        desc, relu, train, has_res = ctx.cfg
-        cout = z.shape[-1]
-        M = z.numel() // cout
+        (desc, train, act, u), role = ctx.cfg, ctx.role
+        sums = ctx.bn_out.take_sums(dy) if ctx.bn_out is not None else None   # asks whether dy IS the consumer's dx: ask first
         dy = dy.contiguous()
-        st = _stream(x)
-        link_in, link_out, res_link = ctx.links
         with torch.cuda.device(x.device):
-            # Residual branch gradient g = dy (.) [y > 0].  When its consumer is one of our own nodes (the block's conv1
-            # data gradient through link_out, or the shortcut unit through res_link) it takes dy and the byte mask
-            # instead, and g is never written.
-            deferred = has_res and mask is not None and (link_out is not None or res_link is not None)
-            hdt = _BF if ctx.act else torch.float32     # dz (to the convolution gradients) and g (to the residual input)
-            bio = (HP_BN_DY if _h(dy) else 0) | (HP_BN_DZ if ctx.act else 0) | (HP_BN_Z if _h(z) else 0)
-            g = torch.empty_like(z, dtype=hdt) if (has_res and not deferred) else None
-            in_mask, relu_flag = mask, relu
-            if res_link is not None and not has_res and res_link.mask is not None:
-                # shortcut unit (no ReLU of its own): the incoming dy still lacks the residual unit's output mask
-                in_mask, relu_flag, res_link.mask = res_link.mask, True, None
-            dgamma = torch.empty_like(gamma)
-            dbeta = torch.empty_like(gamma)
-            nws = (int(L.hp_bn_backward_workspace_bytes(cout)) + 15) // 16 * 16
-            if res_link is not None and not has_res and res_link.done is not None:
-                # shortcut unit whose BatchNorm backward was already run by the residual unit (dual pass below)
-                (dz, dgamma, dbeta), res_link.done = res_link.done, None
-            elif deferred and res_link is not None and res_link.short is not None and cout <= 1024:
-                (zb, mb, rb, gb, trb), res_link.short = res_link.short, None
-                dz = torch.empty_like(z, dtype=hdt)
-                dzb, dgb, dbb = torch.empty_like(zb, dtype=hdt), torch.empty_like(gb), torch.empty_like(gb)
-                ws = torch.empty(2 * nws // 4 + 8, dtype=torch.float32, device=x.device)
-                _lib.check(L.hp_bn_backward_dual(dy.data_ptr(), mask.data_ptr(), M, cout, z.data_ptr(), dz.data_ptr(),
-                                                 mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), 1 if train else 0,
-                                                 dgamma.data_ptr(), dbeta.data_ptr(), zb.data_ptr(), dzb.data_ptr(), mb.data_ptr(),
-                                                 rb.data_ptr(), gb.data_ptr(), 1 if trb else 0, dgb.data_ptr(), dbb.data_ptr(),
-                                                 ws.data_ptr(), bio, st), "hp_bn_backward_dual")
-                res_link.done = (dzb, dgb, dbb)
-            elif (ctx.bn_links[1] is not None and ctx.bn_links[1].sums is not None and g is None and dy.dtype == torch.float32
-                  and ((not has_res and in_mask is None) or (has_res and deferred and in_mask is mask))):
-                # the consumer's data gradient already took this unit's two sums (BnLink): coefficient kernel + apply pass only
-                # (a block's output unit: the apply pass gates dy with the same byte mask the sums were taken with)
-                sums, ctx.bn_links[1].sums = ctx.bn_links[1].sums, None
-                dz = torch.empty_like(z, dtype=hdt)
-                ws = torch.empty(nws // 4 + 2, dtype=torch.float32, device=x.device)
-                _lib.check(L.hp_bn_backward_presummed(dy.data_ptr(), z.data_ptr(), dz.data_ptr(), M, cout, mean.data_ptr(),
-                                                      rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1 if relu_flag else 0,
-                                                      1 if train else 0, dgamma.data_ptr(), dbeta.data_ptr(), _lib.ptr(in_mask),
-                                                      sums.data_ptr(), ws.data_ptr(), bio, st), "hp_bn_backward_presummed")
-            else:
-                dz = torch.empty_like(z, dtype=hdt)
-                ws = torch.empty(nws // 4 + 2, dtype=torch.float32, device=x.device)
-                _lib.check(L.hp_bn_backward(dy.data_ptr(), None, z.data_ptr(), _lib.ptr(g), dz.data_ptr(), M, cout,
-                                            mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                            1 if relu_flag else 0, 1 if train else 0, dgamma.data_ptr(), dbeta.data_ptr(),
-                                            _lib.ptr(in_mask), ws.data_ptr(), bio, st), "hp_bn_backward")
+            dz, dgamma, dbeta, g = _bn_unit_backward(role, u.res, sums, dy, z, mask, mean, rstd, gamma, beta, u.relu, train, act,
+                                                     _stream(x))
             addend = addend_mask = None
             last = True
-            if link_in is not None and ctx.needs_input_grad[0]:
-                addend, addend_mask, last = link_in.take()
+            if u.grad_in is not None and ctx.needs_input_grad[0]:
+                addend, addend_mask, last = u.grad_in.take()
             # (a block input reaches two convolutions: its gradient is complete only in the one that runs last)
-            dx, dw = _conv_grads(desc, x, w, dz, ctx.needs_input_grad[0], addend, addend_mask, bn_in=ctx.bn_links[0] if last else None,
+            dx, dw = _conv_grads(desc, x, w, dz, ctx.needs_input_grad[0], addend, addend_mask, bn_in=u.bn_in if last else None,
                                  force_main=_side.release(ctx, w))
             if not last:           # first of two convolutions reading the block input: park the partial sum
-                link_in.g, dx = dx, None
-            gres = g
-            if link_out is not None and has_res:   # identity shortcut: hand the gradient to the block's conv1 data gradient
-                if deferred:
-                    link_out.g, link_out.mask, gres = dy, mask, None
-                else:
-                    link_out.g, gres = g, None
-            elif deferred:                         # shortcut unit: it receives dy itself and masks it on the fly
-                res_link.mask, gres = mask, dy
-        return dx, dw, dgamma, dbeta, gres, None, None, None, None, None, None, None, None, None, None, None
+                u.grad_in.park(dx)
+                dx = None
+            if role == _OUT_IDENTITY:      # the block's conv1 data gradient adds dy through the byte mask: g is never written
+                u.grad_out.park(dy, mask)
+            elif role == _OUT_SHORTCUT:    # the shortcut unit receives dy itself and masks it on the fly
+                u.res.give("mask", mask)
+                g = dy
+        return dx, dw, dgamma, dbeta, g, None
 
 
 class _ConvBiasToNCDHW(torch.autograd.Function):
@@ -1174,12 +1119,13 @@ class _MaxPool3CL(torch.autograd.Function):
 
 def conv_bn_act(x, conv, bn, relu=True, residual=None, link_in=None, link_out=None, res_link=None, bn_in=None, bn_out=None):
     """x channels-last (B,D,H,W,C).  bn_in / bn_out: BnLinks to the unit that produced x / to the one consumer of the output."""
-    return _ConvBnAct.apply(x, conv.weight, bn.weight, bn.bias, residual, bn, conv.kernel_size[0], conv.stride[0],
-                            conv.padding[0], False, relu, link_in, link_out, res_link, bn_in, bn_out)
+    return _ConvBnAct.apply(x, conv.weight, bn.weight, bn.bias, residual,
+                            _Unit(bn, conv.kernel_size[0], conv.stride[0], conv.padding[0], False, relu, link_in, link_out, res_link,
+                                  bn_in, bn_out))
 
 
 def deconv_bn_relu(x, deconv, bn, bn_in=None, bn_out=None):
-    return _ConvBnAct.apply(x, deconv.weight, bn.weight, bn.bias, None, bn, 4, 2, 1, True, True, None, None, None, bn_in, bn_out)
+    return _ConvBnAct.apply(x, deconv.weight, bn.weight, bn.bias, None, _Unit(bn, 4, 2, 1, True, True, bn_in=bn_in, bn_out=bn_out))
 
 
 class _StemConvBnReluPool(torch.autograd.Function):
@@ -1196,23 +1142,7 @@ class _StemConvBnReluPool(torch.autograd.Function):
         b, d, h, wd_, _ = x.shape
         st = _stream(x)
         with torch.cuda.device(x.device):
-            wf, _ = _pack(desc, w, True, False)
-            z = torch.empty(b, d, h, wd_, cout, dtype=torch.float32, device=x.device)
-            M = z.numel() // cout
-            train = bn.training
-            stats = torch.empty(_lib.STATS_SLOTS * 2 * cout, dtype=torch.float64, device=x.device) if train else None
-            _lib.check(L.hp_conv3d_forward(_C.byref(desc), x.data_ptr(), wf.data_ptr(), None, z.data_ptr(), _lib.ptr(stats), st),
-                       "hp_conv3d_forward")
-            mean = torch.empty(cout, dtype=torch.float32, device=x.device)
-            rstd = torch.empty_like(mean)
-            if train:
-                mom = 0.1 if bn.momentum is None else bn.momentum
-                _lib.check(L.hp_bn_train_finalize_counted(stats.data_ptr(), M, cout, bn.eps, mom, mean.data_ptr(), rstd.data_ptr(),
-                                                          bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                                          bn.num_batches_tracked.data_ptr(), st), "hp_bn_train_finalize")
-            else:
-                _lib.check(L.hp_bn_eval_stats(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), cout, bn.eps,
-                                              mean.data_ptr(), rstd.data_ptr(), st), "hp_bn_eval_stats")
+            z, mean, rstd, train = _conv_bn_stats(desc, x, w, bn, False, st)    # fp32 x, z and weights
             pooled = torch.empty(b, d // 2, h // 2, wd_ // 2, cout, dtype=torch.float32, device=x.device)
             ws = torch.empty(int(L.hp_stem_bn_pool_workspace_bytes(cout)) // 4 + 4, dtype=torch.float32, device=x.device)
             _lib.check(L.hp_stem_bn_relu_pool_forward(z.data_ptr(), pooled.data_ptr(), b, d, h, wd_, cout, mean.data_ptr(),

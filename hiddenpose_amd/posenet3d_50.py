@@ -35,14 +35,14 @@ class Bottleneck(nn.Module):
     def forward(self, x):
         # The block input feeds two consumers; their gradients are summed inside the data-gradient GEMM that
         # finishes last (hip_ops.GradLink) instead of by a separate accumulation pass.
-        link = ops.GradLink() if (torch.is_grad_enabled() and x.requires_grad) else None
+        # (takers: conv1 and the shortcut convolution; with an identity shortcut conv1 alone, which adds what conv3's node parks)
+        shortcut = self.downsample is not None
+        link = ops.GradLink(2 if shortcut else 1) if (torch.is_grad_enabled() and x.requires_grad) else None
         # the BatchNorm-backward sums of the PREVIOUS block's output unit are taken by this block's conv1 data gradient when that is
         # where the block-input gradient becomes complete: identity blocks with a gradient link (hip_ops.offer_res_bn)
-        prev_out = ops.take_res_bn(x)
-        if self.downsample is not None or link is None:
-            prev_out = None
+        prev_out = ops.take_res_bn(x) if (link is not None and not shortcut) else None
         res = rl = None
-        if self.downsample is not None:
+        if shortcut:
             # The shortcut unit is recorded FIRST so that its backward runs LAST: conv1's dense data gradient then
             # writes d(block input) and the strided shortcut gradient is added to it in place at the voxels it
             # reaches (the other order zero-fills a full-size tensor that conv1 has to read back as its addend).
@@ -53,13 +53,9 @@ class Bottleneck(nn.Module):
         b1, b2 = ops.bn_link(), ops.bn_link()
         o = ops.conv_bn_act(x, self.conv1, self.bn1, relu=True, link_in=link, bn_in=prev_out, bn_out=b1)
         o = ops.conv_bn_act(o, self.conv2, self.bn2, relu=True, bn_in=b1, bn_out=b2)
-        if self.downsample is not None:
-            if link is not None:
-                link.arrivals = 2      # conv1 and the shortcut convolution both produce d(block input)
+        if shortcut:
             return ops.conv_bn_act(o, self.conv3, self.bn3, relu=True, residual=res, res_link=rl, bn_in=b2)
-        if link is not None:
-            link.arrivals = 1          # conv1 adds the identity-shortcut gradient parked by conv3's node
-        b3 = ops.bn_link() if (link is not None and ops._BN_FUSE_RES) else None
+        b3 = ops.bn_link(block_output=True) if link is not None else None
         y = ops.conv_bn_act(o, self.conv3, self.bn3, relu=True, residual=x, link_out=link, bn_in=b2, bn_out=b3)
         ops.offer_res_bn(y, b3)
         return y
